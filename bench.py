@@ -3,15 +3,27 @@ on MI355X, points/s on a dense 128^3 grid, batch 4 scenes per GPU (BASELINE.json
 SURVEY.md §8(d) cfg2).  One process per GPU; for N>1 launch with torch.distributed.run.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp8|fp32] [--grid 128]
+                    [--full] [--dump-outputs DIR]
 
 --dtype fp8 is BASELINE.json configs[4] (cfg5): the bf16 step with the 1024-wide layer's
 activation a5 and global_feat's GEMMs in e4m3 on MX-scaled MFMA.
 
 Prints ONE JSON line (rank 0).  value = points processed by all ranks / max-over-ranks
-wall time of K steps (bracketed by barrier + synchronize).  ``roofline`` describes the
-dominant kernel from HIP events recorded on its launch stream inside the timed region;
-``cpu_baseline`` times the pure-PyTorch CPU restatement of the reference step (and the numpy
-oracle) on the host cores.
+wall time of K steps (bracketed by barrier + synchronize); ``ms_per_step`` is that wall time
+over K.  A plain run does nothing else: it sets up, warms up, times the K steps and prints
+the line (``roofline``, ``northstar_64x64`` and ``cpu_baseline`` are null).
+
+``--full`` adds everything else the benchmark measures: ``roofline`` describes the dominant
+kernel from HIP events recorded on its launch stream inside the timed region, two extra steps
+after it give the per-kernel table (stderr) and ``northstar_64x64``, and ``cpu_baseline`` times
+the pure-PyTorch CPU restatement of the reference step (and the numpy oracle) on the host
+cores.  ``--no-kernel-timing`` / ``--no-cpu-baseline`` switch single legs of ``--full`` off.
+
+``--dump-outputs DIR`` writes, after the timed steps, what the last timed step handed its
+caller as float32 ``DIR/<name>.npy`` (rank 0): ``loss``, every parameter's gradient
+(``grad.<param>``), the Adam-updated parameters (``param.<param>``) and the BatchNorm running
+statistics (``buffer.<name>``), about 15 MB in all.  Inputs, initial weights and dropout
+seeds are fixed by the arguments, so two builds can be compared array for array.
 
 ``--gpus N`` with N > 1 and no torch.distributed environment starts N ranks itself (a
 torch.distributed.run child, one process per GPU, RCCL); under a launcher WORLD_SIZE must equal
@@ -263,6 +275,22 @@ def shared_class_weights(label_arrays, num_classes, world):
     return class_weights_from_counts(counts, num_classes)
 
 
+def dump_outputs(out_dir, model, loss):
+    """``--dump-outputs``: what the last timed step handed its caller, as float32
+    ``<out_dir>/<name>.npy``: the loss, p.grad and the Adam-updated p of every parameter, and the
+    BatchNorm running statistics (about 15 MB at C=2; everything is written whole)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1)}
+    for n, p in model.named_parameters():
+        arrays[f"grad.{n}"] = p.grad
+        arrays[f"param.{n}"] = p.detach()
+    for n, b in model.named_buffers():
+        if n.endswith(("running_mean", "running_var")):
+            arrays[f"buffer.{n}"] = b
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def launch_ranks(n):
     """``--gpus N`` (N > 1) without a torch.distributed environment: start N ranks, one process
     per GPU, with torch.distributed.run as a CHILD process and return its exit code.  This
@@ -292,8 +320,14 @@ def main():
     ap.add_argument("--grid", type=int, default=128)
     ap.add_argument("--scenes", type=int, default=4)
     ap.add_argument("--classes", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel HIP events "
+                         "(roofline, northstar_64x64, the stderr table) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's loss, gradients, updated "
+                         "parameters and BatchNorm running statistics as float32 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: record no HIP events")
     ap.add_argument("--draw-at-start", action="store_true",
                     help="draw the dropout bits at the start of the forward instead of beside the Gram of a5 (A/B)")
     ap.add_argument("--no-fused-seg12", action="store_true",
@@ -306,6 +340,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
@@ -379,10 +415,10 @@ def main():
     for i in range(args.warmup):
         loss = run_step()
     torch.cuda.synchronize()
-    # inside the timed region only the dominant-kernel candidates (the global_feat GEMMs and
-    # Gram) are bracketed by HIP events, so the measurement barely perturbs the step; the full
-    # per-kernel breakdown comes from two extra steps after it
-    timing = {} if not args.no_kernel_timing else None
+    # --full: inside the timed region only the dominant-kernel candidates (the global_feat GEMMs
+    # and Gram) are bracketed by HIP events, so the measurement barely perturbs the step; the
+    # full per-kernel breakdown comes from two extra steps after it
+    timing = {} if args.full and not args.no_kernel_timing else None
     step.timing = timing
     step.timing_tags = set(TAG_KERNEL)
     if world > 1:
@@ -396,6 +432,8 @@ def main():
         dist.barrier()
     el = time.perf_counter() - t0
     step.timing = None
+    if args.dump_outputs and rank == 0:   # before --full's extra steps move the weights on
+        dump_outputs(args.dump_outputs, model, loss)
     breakdown = {}
     if timing is not None:
         step.timing, step.timing_tags = breakdown, None
@@ -469,7 +507,7 @@ def main():
                       file=sys.stderr)
 
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     if rank == 0:

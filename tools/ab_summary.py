@@ -3,7 +3,8 @@ import json
 import os
 import re
 
-OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
+OUT = os.environ.get("OUT") or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                            "bench_out")
 
 
 def kernels(path):

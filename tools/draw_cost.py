@@ -2,7 +2,7 @@
 pcs_dropout_bits_bounded skipped after the first step's two calls, so every later step reuses the
 first step's keep bits, and compare with a normal run on the same box.
 
-    python tools/draw_cost.py --steps 10 --warmup 3 --no-cpu-baseline"""
+    python tools/draw_cost.py --full --steps 10 --warmup 3 --no-cpu-baseline"""
 import os
 import sys
 

@@ -2,7 +2,7 @@
 engine's 2 (timing only, never a bench line): pcs_dropout_bits_bounded's max_workgroups is
 rewritten before the call.
 
-    DRAW_WG=3 python tools/draw_wg.py --steps 10 --warmup 3 --no-cpu-baseline"""
+    DRAW_WG=3 python tools/draw_wg.py --full --steps 10 --warmup 3 --no-cpu-baseline"""
 import os
 import sys
 

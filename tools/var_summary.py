@@ -6,7 +6,7 @@ import os
 import re
 import sys
 
-d = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out"
+d = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("OUT", "bench_out")
 tags = sys.argv[2:] or ["dgrad:global_feat", "fwd:global_feat", "wgrad:global_feat"]
 rows = {}
 for js in sorted(glob.glob(os.path.join(d, "var_*.json"))):
