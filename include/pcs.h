@@ -508,14 +508,23 @@ int pcs_bn_s2_from_r(float *stats, int64_t num_chunks, int32_t C, const float *R
  * cm[y, argmax_c logits[m, c]] += 1 for every point m with 0 <= labels[m] < C (labels -1 =
  * padding are skipped).  logits: fp32 rows of stride ld; cm: int64 [C, C], accumulated
  * (zero it once per epoch).  1 <= C <= 256 (LDS histogram up to 64 classes, global atomics above).
+ * The argmax is torch.argmax's: the first maximum, and a NaN counts as the maximum (the first
+ * NaN of a row wins, also over +inf), so a diverged run's metrics come from the predictions
+ * the reference would make.
  */
 int pcs_confusion(const float *logits, int64_t ld, const int64_t *labels, int64_t M, int32_t C,
                   int64_t *cm, pcs_stream_t stream);
 
-/* out[m] = argmax_c logits[m, c] (first maximum; int64), the inference path of P:448-452 */
+/* out[m] = argmax_c logits[m, c] (int64), the inference path of P:448-452.  torch.argmax's
+ * rule: the first maximum; a NaN counts as the maximum, so a row with NaNs gives its first
+ * NaN ([1, nan, 3] -> 1, [1, inf, nan] -> 2). */
 int pcs_argmax(const float *logits, int64_t ld, int64_t M, int32_t C, int64_t *out, pcs_stream_t stream);
 
-/* out[i] = scale * sum_s partial[s*len + i]  (fixed order) */
+/* out[(i / row_len) * out_stride_rows + i % row_len] = scale * sum_s partial[s*len + i]  (fixed
+ * order; the columns of an output row beyond row_len are not written).  When row_len % 4 == 0
+ * the kernel loads and stores 16 bytes at a time: partial, out, len and out_stride_rows must
+ * then be multiples of 4 floats (16-byte aligned pointers).  Any other row_len takes a scalar
+ * path with no alignment requirement. */
 int pcs_reduce_partials(const float *partial, int64_t nslabs, int64_t len, float scale,
                         float *out, int64_t out_stride_rows, int64_t row_len,
                         pcs_stream_t stream);

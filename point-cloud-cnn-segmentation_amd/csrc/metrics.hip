@@ -1,5 +1,6 @@
 // Device confusion matrix for the training/validation metrics (P:261-266, P:299-346):
-// prediction = argmax over the C logits of a point (first maximum), rows = true label,
+// prediction = argmax over the C logits of a point (first maximum; a NaN counts as the
+// maximum and the first NaN wins, as torch.argmax), rows = true label,
 // columns = prediction, labels < 0 (padding, P:54) skipped.  Accumulates into cm (int64
 // [C, C]) so a whole epoch needs one host read.
 #include "common.h"
@@ -26,7 +27,7 @@ __global__ __launch_bounds__(THREADS) void confusion_kernel(const float *__restr
     float bz = z[0];
     for (int c = 1; c < C; ++c) {
       const float v = z[c];
-      if (v > bz) { bz = v; best = c; }
+      if (v > bz || (v != v && bz == bz)) { bz = v; best = c; }   // torch.argmax: the first NaN wins
     }
     if constexpr (LDS) atomicAdd(&hist[(int)y * C + best], 1u);
     else atomicAdd(&cm[(int)y * C + best], 1ull);
@@ -64,15 +65,18 @@ __global__ void argmax_kernel(const float *__restrict__ logits, int64_t ld, int6
     const float *z = logits + m * ld;
     int best = 0;
     float bz = z[0];
-    for (int c = 1; c < C; ++c)
-      if (z[c] > bz) { bz = z[c]; best = c; }
+    for (int c = 1; c < C; ++c) {
+      const float v = z[c];
+      if (v > bz || (v != v && bz == bz)) { bz = v; best = c; }   // torch.argmax: the first NaN wins
+    }
     out[m] = best;
   }
 }
 
 }  // namespace
 
-// predictions = argmax over classes (first maximum), the inference path of P:448-452
+// predictions = argmax over classes (first maximum, the first NaN if there is one), the
+// inference path of P:448-452
 extern "C" int pcs_argmax(const float *logits, int64_t ld, int64_t M, int32_t C, int64_t *out,
                           pcs_stream_t stream) {
   if (!logits || !out || M < 0 || C < 1 || ld < C) return pcs_set_einval("pcs_argmax", "bad arguments");
