@@ -321,6 +321,8 @@ int pcs_pool_bwd(const pcs_pool_bwd_args *args, pcs_stream_t stream);
  *                then the seg_conv4 backward: dz_s3 = relu'(z)*(dlogits W), S1/S2 partials,
  *                dW_s4 / db_s4 partials;
  *  PCS_HEAD_BWD: the same backward from caller-supplied dlogits (autograd drop-in path).
+ * A label outside [0, C) is ignored like -1 (zero loss and gradient for its row), whatever its
+ * low 32 bits; every kernel behind pcs_head agrees on this (tests/test_gpu_head.py).
  */
 enum { PCS_HEAD_FWD = 0, PCS_HEAD_CE = 1, PCS_HEAD_BWD = 2 };
 typedef struct {

@@ -1,7 +1,7 @@
-"""fp64 restatements of the small glue kernels of csrc/small.hip, from their descriptions in
-include/pcs.h (not a test module).  tests/test_small_refs.py proves them against torch in fp64
-on the CPU; the GPU tests (test_gpu_small_kernels.py, test_gpu_conv1.py, test_gpu_colstats.py)
-compare the kernels with them.
+"""fp64 restatements of the small glue kernels of csrc/small.hip and of the segmentation head,
+from their descriptions in include/pcs.h (not a test module).  tests/test_small_refs.py proves
+them against torch in fp64 on the CPU; the GPU tests (test_gpu_small_kernels.py,
+test_gpu_conv1.py, test_gpu_colstats.py, test_gpu_head.py) compare the kernels with them.
 
 Everything is NumPy float64.  The partial generators build the per-chunk records the GEMM
 epilogues hand to the finalize kernels; they compute in fp64 and round to fp32 last
@@ -243,6 +243,109 @@ def scene_gemv_ref(g, W, col_off, bias):
     bb = f64(bias) if bias is not None else np.zeros(Wg.shape[0])
     v = g @ Wg.T + bb
     return v, sum_bound(g.shape[1] + 1, np.abs(g) @ np.abs(Wg).T + np.abs(bb))
+
+
+# ---------------------------------------------------------------------------------------
+# segmentation head
+# ---------------------------------------------------------------------------------------
+HEAD_FWD, HEAD_CE, HEAD_BWD = 0, 1, 2
+# expf / logf error in ulps (2^-23 relative each).  The ROCm install documents neither in its
+# shipped math documentation, so 2 ulp each is assumed.
+EXP_ULPS = LOG_ULPS = 2.0
+
+
+def head_ref(Y, s, t, mean, rstd, W, bias, mode, labels=None, class_weight=None, wsum=None, dlogits=None):
+    """pcs_head: seg_conv4 on a = relu(Y*s + t), and by mode the weighted cross entropy with its
+    gradient (HEAD_CE; labels outside [0, C) are ignored, wsum None = 1) or caller-supplied
+    dlogits (HEAD_BWD), then the backward: dz = (a > 0) * (dl W), S1 = sum_m dz,
+    S2 = sum_m dz * (Y - mean) * rstd, dW = dl^T a, db = sum_m dl.
+
+    Returns a dict of the fp64 results and, as ``abs_<name>``, the sum of the absolute terms each
+    one is a sum of (what its rounding errors scale with).  CE also returns the per-row pieces
+    (valid, w, lse, mx, p, nll) that head_bounds propagates through exp and log."""
+    Y, s, t, W, bias = f64(Y), f64(s), f64(t), f64(W), f64(bias)
+    z = Y * s + t
+    a = np.maximum(z, 0.0)
+    out = dict(z=z, a=a, logits=a @ W.T + bias, abs_logits=np.abs(a) @ np.abs(W).T + np.abs(bias))
+    if mode == HEAD_FWD:
+        return out
+    lg = out["logits"]
+    M, C = lg.shape
+    if mode == HEAD_CE:
+        lab = np.asarray(labels, np.int64)
+        valid = (lab >= 0) & (lab < C)
+        li = np.where(valid, lab, 0)
+        w = np.where(valid, f64(class_weight)[li], 0.0)
+        g = 1.0 if wsum is None else 1.0 / float(wsum)
+        mx = lg.max(1)
+        lse = mx + np.log(np.exp(lg - mx[:, None]).sum(1))
+        p = np.exp(lg - lse[:, None])
+        onehot = np.zeros((M, C))
+        onehot[np.arange(M), li] = 1.0
+        nll = lse - lg[np.arange(M), li]
+        dl = (w * g)[:, None] * (p - onehot)
+        out.update(valid=valid, label=li, w=w, gscale=g, mx=mx, lse=lse, p=p, onehot=onehot, nll=nll,
+                   row_loss=w * nll, loss_sum=float((w * nll).sum()), abs_loss_sum=float((w * np.abs(nll)).sum()))
+    else:
+        dl = f64(dlogits)
+        assert dl.shape == (M, C)
+    mean, rstd = f64(mean), f64(rstd)
+    gate = a > 0
+    dz = np.where(gate, dl @ W, 0.0)
+    xhat = (Y - mean) * rstd
+    # S2 is evaluated as sum dz*xhat or as rstd*(sum dz*Y - mean*sum dz): the terms of either
+    xabs = (np.abs(Y) + np.abs(mean)) * np.abs(rstd)
+    out.update(dl=dl, dz=dz, xhat=xhat, xabs=xabs, abs_dz=np.where(gate, np.abs(dl) @ np.abs(W), 0.0),
+               S1=dz.sum(0), S2=(dz * xhat).sum(0), abs_S1=np.abs(dz).sum(0), abs_S2=(np.abs(dz) * xabs).sum(0),
+               dW=dl.T @ a, db=dl.sum(0), abs_dW=np.abs(dl).T @ np.abs(a), abs_db=np.abs(dl).sum(0))
+    return out
+
+
+def head_bounds(ref, W, mode, rows_per_chunk, bf16_dz=False):
+    """Bounds on an fp32 evaluation of head_ref's outputs (any summation order), from its
+    absolute sums; first order in 2^-24, propagated linearly.
+
+    a       one rounding (the fma of Y*s + t);
+    logits  128 products and the bias on the rounded a;
+    CE      lse = mx + log(sum exp(z - mx)): 1-Lipschitz in the logits, the rounding of z - mx
+            (relative U*|z - mx| on each exp term), EXP_ULPS per exp, C - 1 additions, LOG_ULPS on
+            the log, one rounding of the sum; p = exp(z - lse): the argument's error e enters as
+            expm1(e); dl = (w/wsum)*(p - onehot): the reciprocal, two products, one difference;
+            loss: the row's w*(lse - z_l), then a sum of at most rows_per_chunk terms per chunk;
+    dz      a C-term chain on the inexact dl (plus 2^-8 |ref| for a bf16 store);
+    S1, S2, dW, db  sums of at most rows_per_chunk terms per chunk, of the inexact dz / dl / a."""
+    W = np.abs(f64(W))
+    C = W.shape[0]
+    e_a = round_bound(ref["a"])
+    e_z = sum_bound(W.shape[1] + 1, ref["abs_logits"]) + e_a @ W.T
+    out = dict(a=e_a, logits=e_z)
+    if mode == HEAD_FWD:
+        return out
+    if mode == HEAD_CE:
+        lg, mx, lse, p, w = ref["logits"], ref["mx"], ref["lse"], ref["p"], ref["w"]
+        M = lg.shape[0]
+        pm = np.exp(lg - mx[:, None])
+        pm /= pm.sum(1, keepdims=True)
+        e_log = (U * (pm * np.abs(lg - mx[:, None])).sum(1) + EXP_ULPS * ULP + (C - 1) * U
+                 + LOG_ULPS * ULP * np.abs(lse - mx))
+        e_lse = e_z.max(1) + e_log + round_bound(mx, lse - mx)
+        e_arg = e_z + e_lse[:, None] + round_bound(lg - lse[:, None])
+        e_p = p * (np.expm1(e_arg) + EXP_ULPS * ULP)
+        wg = np.abs(w * ref["gscale"])[:, None]
+        e_dl = wg * e_p + 4.0 * ULP * np.abs(ref["dl"])
+        e_row = w * (e_lse + e_z[np.arange(M), ref["label"]] + round_bound(ref["nll"])) + round_bound(ref["row_loss"])
+        out["loss_sum"] = float(e_row.sum() + sum_bound(rows_per_chunk, ref["abs_loss_sum"]))
+    else:
+        e_dl = np.zeros_like(ref["dl"])
+    gate = ref["a"] > 0
+    e_dz = np.where(gate, sum_bound(C, ref["abs_dz"]) + e_dl @ W, 0.0)
+    n = rows_per_chunk
+    out.update(dl=e_dl, dz=e_dz + (2.0 ** -8 * np.abs(ref["dz"]) if bf16_dz else 0.0),
+               S1=sum_bound(n, ref["abs_S1"]) + e_dz.sum(0),
+               S2=sum_bound(n + 3, ref["abs_S2"]) + (e_dz * ref["xabs"]).sum(0),
+               dW=sum_bound(n, ref["abs_dW"]) + e_dl.T @ np.abs(ref["a"]) + np.abs(ref["dl"]).T @ e_a,
+               db=sum_bound(n, ref["abs_db"]) + e_dl.sum(0))
+    return out
 
 
 # ---------------------------------------------------------------------------------------

@@ -160,6 +160,79 @@ def test_adam_reference(wd):
     _close(a[0], b[0], 1e-15)
 
 
+def _head_inputs(M, C, seed):
+    g = torch.Generator().manual_seed(seed)
+    rnd = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)   # noqa: E731
+    y = (rnd(M, 128) * 1.5 + 0.2).requires_grad_()
+    s = (torch.rand(128, generator=g, dtype=torch.float64) + 0.5) * torch.where(rnd(128) < -0.67, -1.0, 1.0)
+    t, mean, rstd = rnd(128) * 0.5, rnd(128) * 0.3, (rnd(128) * 0.1 + 1.0).abs()
+    W = (rnd(C, 128) * 0.1).requires_grad_()
+    b = (rnd(C) * 0.2).requires_grad_()
+    return g, y, s, t, mean, rstd, W, b
+
+
+@pytest.mark.parametrize("M,C", [(37, 1), (50, 3), (41, 17), (23, 100)])
+@pytest.mark.parametrize("with_wsum", [True, False])
+def test_head_reference_ce(M, C, with_wsum):
+    """head_ref in CE mode is F.cross_entropy (weights, ignore_index=-1) on seg_conv4 of
+    relu(y*s + t) and its gradients; labels outside [0, C) count as ignored."""
+    g, y, s, t, mean, rstd, W, b = _head_inputs(M, C, 10 * M + C)
+    lab = torch.randint(-1, C, (M,), generator=g)
+    cw = torch.rand(C, generator=g, dtype=torch.float64) + 0.5
+    if C > 2:
+        cw[C // 2] = 0.0                                # a class of weight exactly 0
+    lab[0] = C - 1                                      # at least one valid row of non-zero weight
+    valid = lab >= 0
+    D = float(cw[lab[valid]].sum())
+    logits = torch.relu(y * s + t) @ W.T + b
+    loss = F.cross_entropy(logits, lab, weight=cw, ignore_index=-1)      # mean: sum w nll / D
+    loss.backward()
+    odd = lab.clone()
+    odd[~valid] = torch.tensor([-7, C, C + 5, -1])[torch.arange(int((~valid).sum())) % 4]   # all ignored alike
+    ref = R.head_ref(y.detach().numpy(), s.numpy(), t.numpy(), mean.numpy(), rstd.numpy(), W.detach().numpy(),
+                     b.detach().numpy(), R.HEAD_CE, labels=odd.numpy(), class_weight=cw.numpy(),
+                     wsum=D if with_wsum else None)
+    k = 1.0 if with_wsum else D                          # without wsum the gradients are D times torch's
+    _close(ref["logits"], logits.detach().numpy())
+    _close(ref["loss_sum"] / D, loss.item(), 1e-12)
+    _close(ref["dz"] * s.numpy(), y.grad.numpy() * k, 1e-12)
+    _close(ref["dW"], W.grad.numpy() * k, 1e-12)
+    _close(ref["db"], b.grad.numpy() * k, 1e-12)
+    assert (ref["dl"][~valid.numpy()] == 0).all() and (ref["dz"][ref["a"] == 0] == 0).all()
+    xh = (y.detach().numpy() - mean.numpy()) * rstd.numpy()
+    _close(ref["S1"], ref["dz"].sum(0), 1e-13)
+    _close(ref["S2"], (ref["dz"] * xh).sum(0), 1e-13)
+    # the absolute sums dominate what they bound, and the bounds are finite and non-negative
+    for name in ("logits", "dz", "S1", "S2", "dW", "db"):
+        assert (ref["abs_" + name] >= np.abs(ref[name]) - 1e-13).all(), name
+    assert ref["abs_loss_sum"] >= abs(ref["loss_sum"])
+    for name, e in R.head_bounds(ref, W.detach().numpy(), R.HEAD_CE, 64, bf16_dz=True).items():
+        e = np.asarray(e)
+        assert np.isfinite(e).all() and (e >= 0).all(), name
+        if name in ref:
+            assert e.shape == np.shape(ref[name]), name
+
+
+@pytest.mark.parametrize("M,C", [(37, 2), (29, 65)])
+def test_head_reference_bwd(M, C):
+    """head_ref in BWD mode is torch.autograd.grad of the logits with the given dlogits."""
+    g, y, s, t, mean, rstd, W, b = _head_inputs(M, C, 3 * M + C)
+    dlog = torch.randn(M, C, generator=g, dtype=torch.float64)
+    logits = torch.relu(y * s + t) @ W.T + b
+    gy, gW, gb = torch.autograd.grad(logits, (y, W, b), dlog)
+    ref = R.head_ref(y.detach().numpy(), s.numpy(), t.numpy(), mean.numpy(), rstd.numpy(), W.detach().numpy(),
+                     b.detach().numpy(), R.HEAD_BWD, dlogits=dlog.numpy())
+    _close(ref["logits"], logits.detach().numpy())
+    _close(ref["dz"] * s.numpy(), gy.numpy(), 1e-12)
+    _close(ref["dW"], gW.numpy(), 1e-12)
+    _close(ref["db"], gb.numpy(), 1e-12)
+    xh = (y.detach().numpy() - mean.numpy()) * rstd.numpy()
+    _close(ref["S2"], (ref["dz"] * xh).sum(0), 1e-13)
+    fwd = R.head_ref(y.detach().numpy(), s.numpy(), t.numpy(), None, None, W.detach().numpy(),
+                     b.detach().numpy(), R.HEAD_FWD)
+    assert np.array_equal(fwd["logits"], ref["logits"]) and "dz" not in fwd
+
+
 def test_scene_gemv_reference_and_bounds():
     g = torch.Generator().manual_seed(5)
     x = torch.randn(3, 10, generator=g, dtype=torch.float64)
