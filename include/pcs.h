@@ -731,7 +731,33 @@ int pcs_conv3d_weight_t(const void *W, int32_t Cout, int32_t taps, int32_t Cin, 
  * pcs_sparse_conv_wgrad_pairs: pcs_sparse_conv_wgrad's dW / db over the pairs only (dW_t = sum over
  *   tap t's pairs of dY[pair_out] (x) X[pair_in]); tap_off a host array; Cin, Cout % 64 == 0;
  *   fixed-order partial sums (deterministic).
+ *
+ * Coarse level of a k = 2, s = 2 convolution (the occupied-only U-Net's down / up step).  With an
+ * even grid G and Gc = G / 2, a fine voxel (scene, ix, iy, iz) has the parent key scene * Gc^3 +
+ * ((ix >> 1) * Gc + (iy >> 1)) * Gc + (iz >> 1) and sits at tap ((ix & 1) * 2 + (iy & 1)) * 2 +
+ * (iz & 1) of it (the tap order of a torch Conv3d weight [Cout, Cin, 2, 2, 2] on a dense
+ * [B, C, G(x), G(y), G(z)] grid).  The coarse voxels are the unique parent keys.
+ * pcs_sparse_coarse_keys: parent_key [n] u64 and tap [n] i32 of the fine keys; an odd grid is
+ *   rejected.
+ * pcs_sparse_coarse_maps: from coarse_row [n_fine] i64 (the row of each fine voxel's parent among
+ *   the coarse voxels) and tap: child [n_coarse][8] i32 (row of the fine voxel at tap t, or -1),
+ *   parent [n_fine] i32, and the one-hot up map up [n_fine][8] i32 (parent[f] at column tap[f], -1
+ *   elsewhere); n_coarse <= n_fine < 2^28 (the pair lists need n_fine * 8 < 2^31).  child and up are
+ *   neighbour maps of 8 taps: pcs_sparse_conv, pcs_sparse_conv_wgrad
+ *   and pcs_sparse_pairs_* take them as they are.
+ * pcs_sparse_conv_rows: Y[pair_out[p]] = b + W[t] X[pair_in[p]] for every pair p of tap t, written
+ *   directly in ydtype (no Z workspace, no reduce pass), for pair lists in which every output row
+ *   0 .. M - 1 occurs in exactly one pair (tap_off[taps] == M is checked; the lists of the up map).
+ *   X bf16 [*, Cin], W bf16 [Cout][taps][Cin], Y [M, Cout]; tap_off a HOST array; Cin % 32 == 0,
+ *   Cout % 64 == 0, 1 <= taps <= 27.  A tap without pairs launches no tile.
  */
+int pcs_sparse_coarse_keys(const uint64_t *keys, int64_t n, int32_t grid, uint64_t *parent_key, int32_t *tap,
+                           pcs_stream_t stream);
+int pcs_sparse_coarse_maps(const int64_t *coarse_row, const int32_t *tap, int64_t n_fine, int64_t n_coarse,
+                           int32_t *child, int32_t *parent, int32_t *up, pcs_stream_t stream);
+int pcs_sparse_conv_rows(const int32_t *pair_in, const int32_t *pair_out, const int64_t *tap_off, int32_t taps,
+                         int64_t M, const void *X, int32_t Cin, const void *W, int32_t Cout, const float *bias,
+                         void *Y, int32_t ydtype, pcs_stream_t stream);
 int pcs_voxel_keys(const float *points, const int64_t *offsets, int64_t num_scenes, int64_t T, int32_t grid,
                    float lo_x, float lo_y, float lo_z, float hi_x, float hi_y, float hi_z,
                    const int64_t *voxel_of_point, uint64_t *keys, pcs_stream_t stream);

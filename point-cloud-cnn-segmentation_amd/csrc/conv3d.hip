@@ -1106,14 +1106,13 @@ __global__ __launch_bounds__(256) void pairs_build_kernel(const int32_t *__restr
   for (int i = tid; i < nr * taps; i += 256) ppos[r0 * taps + i] = rb[i];
 }
 
-// Z[p][n0 ..] = W[tw(t)] X[pair_in[p]] for the 64 pairs of one tile of tap t (fp32 products).
-// (Reducing in the centre tap's GEMM epilogue instead of a separate pass, the centre's products
-// never stored, was slower: 26 dependent gathers per lane there against 8 threads per row here.)
+// The tile loop of the two pair GEMMs below: acc = W[tw(t)] X[pair_in[p]] (fp32) for the 64 pairs
+// [p0, pend) of tile blockIdx.x, which belongs to tap t, and the 64 output channels from
+// blockIdx.y * BN; lane (lr, lg) of wave (wr, wc) holds pairs p0 + wr * 32 + i * 16 + lr, channels
+// n0 + wc * 32 + j * 16 + 4 * lg .. + 3 in acc[i][j].
 template <int KST>
-__global__ __launch_bounds__(THREADS) void pair_gemm_kernel(PairTaps pt, const int32_t *__restrict__ pin,
-                                                            const bf16_t *__restrict__ X, int Cin,
-                                                            const bf16_t *__restrict__ W, int Cout, int flip,
-                                                            float *__restrict__ Z) {
+PCS_DEV void pair_tile(const PairTaps &pt, const int32_t *__restrict__ pin, const bf16_t *__restrict__ X, int Cin,
+                       const bf16_t *__restrict__ W, int flip, f32x4 (&acc)[2][2], int64_t &p0, int64_t &pend) {
   constexpr int BMT = 64, RB = KST * 2, CPR = KST / 8, RPP = THREADS / CPR;
   constexpr int HA = BMT / RPP, HB = BN / RPP, KK = KST / 32;
   __shared__ __attribute__((aligned(16))) char lds[2][(BMT + BN) * RB];
@@ -1124,7 +1123,8 @@ __global__ __launch_bounds__(THREADS) void pair_gemm_kernel(PairTaps pt, const i
   int t = 0;
   while (t + 1 < taps && pt.tile_off[t + 1] <= tile) ++t;
   const int tw = flip ? taps - 1 - t : t;
-  const int64_t p0 = pt.tap_off[t] + (int64_t)(tile - pt.tile_off[t]) * BMT, pend = pt.tap_off[t + 1];
+  p0 = pt.tap_off[t] + (int64_t)(tile - pt.tile_off[t]) * BMT;
+  pend = pt.tap_off[t + 1];
   const int n0 = blockIdx.y * BN;
   const int srow = tid / CPR, q = tid % CPR;
   int iv[HA];
@@ -1158,7 +1158,6 @@ __global__ __launch_bounds__(THREADS) void pair_gemm_kernel(PairTaps pt, const i
       *reinterpret_cast<u32x4 *>(tB + r * RB + swzf(r, q) * 16) = rb[h];
     }
   };
-  f32x4 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1191,6 +1190,22 @@ __global__ __launch_bounds__(THREADS) void pair_gemm_kernel(PairTaps pt, const i
     if (ks + 1 < nks) stage(buf ^ 1);
     __syncthreads();
   }
+}
+
+// Z[p][n0 ..] = W[tw(t)] X[pair_in[p]] for the 64 pairs of one tile of tap t (fp32 products).
+// (Reducing in the centre tap's GEMM epilogue instead of a separate pass, the centre's products
+// never stored, was slower: 26 dependent gathers per lane there against 8 threads per row here.)
+template <int KST>
+__global__ __launch_bounds__(THREADS) void pair_gemm_kernel(PairTaps pt, const int32_t *__restrict__ pin,
+                                                            const bf16_t *__restrict__ X, int Cin,
+                                                            const bf16_t *__restrict__ W, int Cout, int flip,
+                                                            float *__restrict__ Z) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
+  const int n0 = blockIdx.y * BN;
+  f32x4 acc[2][2];
+  int64_t p0, pend;
+  pair_tile<KST>(pt, pin, X, Cin, W, flip, acc, p0, pend);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int64_t p = p0 + wr * 32 + i * 16 + lr;
@@ -1230,6 +1245,47 @@ __global__ __launch_bounds__(256) void pair_reduce_kernel(const int32_t *__restr
   } else {
     *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(Y) + m * Cout + c) = a;
     *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(Y) + m * Cout + c + 4) = b;
+  }
+}
+
+// Y[pair_out[p]] = b + W[t] X[pair_in[p]] for the 64 pairs of one tile of tap t, where every output
+// row has exactly one pair (the up-convolution of a k = 2, s = 2 level, and the down-convolution's
+// input gradient: a fine voxel has one parent and sits at one tap of it).  pair_gemm_kernel's
+// tile loop with sparse_conv_kernel's epilogue scattered through pair_out: no Z, no reduce pass.
+template <int KST, bool OUT_BF16>
+__global__ __launch_bounds__(THREADS) void pair_rows_kernel(PairTaps pt, const int32_t *__restrict__ pin,
+                                                            const int32_t *__restrict__ pout,
+                                                            const bf16_t *__restrict__ X, int Cin,
+                                                            const bf16_t *__restrict__ W, int Cout,
+                                                            const float *__restrict__ bias, int64_t M,
+                                                            void *__restrict__ Y) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
+  const int n0 = blockIdx.y * BN;
+  f32x4 acc[2][2];
+  int64_t p0, pend;
+  pair_tile<KST>(pt, pin, X, Cin, W, 0, acc, p0, pend);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int64_t p = p0 + wr * 32 + i * 16 + lr;
+    if (p >= pend) continue;
+    const int64_t uo = pout[p];
+    if (uo < 0 || uo >= M) continue;   // (not a row of Y: a list that breaks the precondition)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int co = n0 + wc * 32 + j * 16 + 4 * lg;
+      float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+      if (bias) {
+        const float4 bb = *reinterpret_cast<const float4 *>(bias + co);
+        v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
+      }
+      if constexpr (OUT_BF16) {
+        *reinterpret_cast<uint2 *>(reinterpret_cast<bf16_t *>(Y) + uo * Cout + co) =
+            make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
+      } else {
+        *reinterpret_cast<float4 *>(reinterpret_cast<float *>(Y) + uo * Cout + co) = make_float4(v[0], v[1], v[2], v[3]);
+      }
+    }
   }
 }
 
@@ -1600,6 +1656,35 @@ extern "C" int pcs_sparse_conv_pairs(const int32_t *pair_in, const int32_t *pair
     else hipLaunchKernelGGL(pair_reduce_kernel<false>, g, dim3(256), 0, s, pair_pos, M, (int)taps, Z, (int)Cout, bias, Y);
     PCS_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+extern "C" int pcs_sparse_conv_rows(const int32_t *pair_in, const int32_t *pair_out, const int64_t *tap_off, int32_t taps,
+                                    int64_t M, const void *X, int32_t Cin, const void *W, int32_t Cout,
+                                    const float *bias, void *Y, int32_t ydtype, pcs_stream_t stream) {
+  PairTaps pt;
+  const char *why = pair_taps(tap_off, taps, &pt);
+  if (why) return pcs_set_einval("pcs_sparse_conv_rows", why);
+  if (!X || !W || !Y || M < 0 || Cin <= 0 || Cout <= 0 || Cin % KS != 0 || Cout % BN != 0 ||
+      (ydtype != PCS_F32 && ydtype != PCS_BF16) || (tap_off[taps] > 0 && (!pair_in || !pair_out)))
+    return pcs_set_einval("pcs_sparse_conv_rows", "bad arguments (Cin % 32 == 0, Cout % 64 == 0, Y f32 | bf16)");
+  if (tap_off[taps] != M)
+    return pcs_set_einval("pcs_sparse_conv_rows", "every output row needs exactly one pair (tap_off[taps] == M)");
+  const int tiles = pt.tile_off[taps];
+  if (tiles == 0) return 0;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)tiles, (unsigned)(Cout / BN));
+  const bf16_t *Xb = static_cast<const bf16_t *>(X), *Wb = static_cast<const bf16_t *>(W);
+#define PCS_PR(KST, OB) \
+  hipLaunchKernelGGL((pair_rows_kernel<KST, OB>), grid, dim3(THREADS), 0, s, pt, pair_in, pair_out, Xb, (int)Cin, Wb, \
+                     (int)Cout, bias, M, Y)
+  if (Cin % 64 == 0) {
+    if (ydtype == PCS_BF16) PCS_PR(64, true); else PCS_PR(64, false);
+  } else {
+    if (ydtype == PCS_BF16) PCS_PR(32, true); else PCS_PR(32, false);
+  }
+#undef PCS_PR
+  PCS_CHECK_LAUNCH();
   return 0;
 }
 

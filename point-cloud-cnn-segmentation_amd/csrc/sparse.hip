@@ -11,6 +11,8 @@
 //                scene, t = (a * 3 + b) * 3 + c, or -1 (empty or outside the grid): the 27 taps of
 //                a 3x3x3 submanifold convolution in the tap order of a torch Conv3d weight
 //                [Cout, Cin, 3, 3, 3] applied to a dense [B, C, G(x), G(y), G(z)] grid.
+//   coarse level the occupied 2x2x2 cells of an even grid (key of the cell on the G / 2 grid) and
+//                the child / parent / up maps of a k = 2, s = 2 convolution between the levels
 #include "common.h"
 
 namespace {
@@ -122,6 +124,43 @@ __global__ __launch_bounds__(THREADS) void neighbors_kernel(const uint64_t *__re
   }
 }
 
+// coarse level of a stride-2 (k = 2) convolution: the parent cell of a fine voxel and the tap
+// (its corner of the 2x2x2 cell) it sits at, t = ((ix & 1) * 2 + (iy & 1)) * 2 + (iz & 1)
+__global__ __launch_bounds__(THREADS) void coarse_keys_kernel(const uint64_t *__restrict__ keys, int64_t n, int G,
+                                                              uint64_t *__restrict__ pkey, int32_t *__restrict__ tap) {
+  const uint64_t G3 = (uint64_t)G * G * G, Gc = (uint64_t)(G >> 1), Gc3 = Gc * Gc * Gc;
+  for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * THREADS) {
+    const uint64_t k = keys[i];
+    const uint64_t scene = k / G3, loc = k - scene * G3;
+    const uint64_t ix = loc / ((uint64_t)G * G), iy = (loc / G) % G, iz = loc % G;
+    pkey[i] = scene * Gc3 + ((ix >> 1) * Gc + (iy >> 1)) * Gc + (iz >> 1);
+    tap[i] = (int32_t)(((ix & 1) * 2 + (iy & 1)) * 2 + (iz & 1));
+  }
+}
+
+__global__ __launch_bounds__(THREADS) void fill_i32_kernel(int32_t *__restrict__ p, int64_t n, int32_t v) {
+  for (int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * THREADS) p[i] = v;
+}
+
+// one thread per fine voxel f: parent[f], the one-hot row up[f][0..7] and child[parent[f]][tap[f]]
+// = f (child cleared to -1 before).  (coarse row, tap) names one fine voxel, so no two threads
+// write the same child entry.  A row or tap outside its range (not produced by the kernels
+// above) writes nothing but parent[f] = -1 and an empty up row.
+__global__ __launch_bounds__(THREADS) void coarse_maps_kernel(const int64_t *__restrict__ crow,
+                                                              const int32_t *__restrict__ tap, int64_t nf, int64_t nc,
+                                                              int32_t *__restrict__ child, int32_t *__restrict__ parent,
+                                                              int32_t *__restrict__ up) {
+  for (int64_t f = (int64_t)blockIdx.x * THREADS + threadIdx.x; f < nf; f += (int64_t)gridDim.x * THREADS) {
+    const int64_t m = crow[f];
+    const int t = tap[f];
+    const bool ok = m >= 0 && m < nc && t >= 0 && t < 8;
+    parent[f] = ok ? (int32_t)m : -1;
+#pragma unroll
+    for (int a = 0; a < 8; ++a) up[f * 8 + a] = (ok && a == t) ? (int32_t)m : -1;
+    if (ok) child[m * 8 + t] = (int32_t)f;
+  }
+}
+
 int blocks_for_n(int64_t n) {
   const int64_t b = (n + THREADS - 1) / THREADS;
   return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -188,6 +227,36 @@ extern "C" int pcs_sparse_neighbors(const uint64_t *table_keys, const int32_t *t
   hipLaunchKernelGGL(neighbors_kernel, dim3(blocks_for_n(n * 27)), dim3(THREADS), 0,
                      reinterpret_cast<hipStream_t>(stream), table_keys, table_vals, (uint64_t)(capacity - 1), keys, n,
                      (int)grid, nbr);
+  PCS_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- coarse level of a k = 2, s = 2 convolution (see coarse_keys_kernel)
+extern "C" int pcs_sparse_coarse_keys(const uint64_t *keys, int64_t n, int32_t grid, uint64_t *parent_key, int32_t *tap,
+                                      pcs_stream_t stream) {
+  if (grid < 2 || grid > (1 << 20) || (grid & 1) != 0)
+    return pcs_set_einval("pcs_sparse_coarse_keys", "the grid must be even (2 <= grid <= 2^20)");
+  if (n < 0 || n > ((int64_t)1 << 31) || (n > 0 && (!keys || !parent_key || !tap)))
+    return pcs_set_einval("pcs_sparse_coarse_keys", "keys, parent_key and tap are required (0 <= n <= 2^31)");
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(coarse_keys_kernel, dim3(blocks_for_n(n)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+                     keys, n, (int)grid, parent_key, tap);
+  PCS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int pcs_sparse_coarse_maps(const int64_t *coarse_row, const int32_t *tap, int64_t n_fine, int64_t n_coarse,
+                                      int32_t *child, int32_t *parent, int32_t *up, pcs_stream_t stream) {
+  if (n_fine < 0 || n_coarse < 0 || n_coarse > n_fine || n_fine >= ((int64_t)1 << 28) ||
+      (n_fine > 0 && (!coarse_row || !tap || !parent || !up)) || (n_coarse > 0 && !child))
+    return pcs_set_einval("pcs_sparse_coarse_maps",
+                          "coarse_row, tap, child, parent and up are required (n_coarse <= n_fine < 2^28)");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (n_coarse > 0)
+    hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks_for_n(n_coarse * 8)), dim3(THREADS), 0, s, child, n_coarse * 8, -1);
+  if (n_fine > 0)
+    hipLaunchKernelGGL(coarse_maps_kernel, dim3(blocks_for_n(n_fine)), dim3(THREADS), 0, s, coarse_row, tap, n_fine,
+                       n_coarse, child, parent, up);
   PCS_CHECK_LAUNCH();
   return 0;
 }

@@ -13,6 +13,16 @@ neighbours (nbr[v][t], -1 = empty), so an occupied-only network never densifies.
 map is built once per voxelisation (pcs_voxel_hash_build + pcs_sparse_neighbors) and shared by
 every layer at that resolution, forward and backward (the input gradient is the same gather with
 the transposed, tap-flipped weight).
+
+A U-Net changes resolution with the 2x2x2, stride-2 pair, still on occupied voxels only:
+
+    svc, link = coarsen(sv)                              # grid / 2: the occupied 2x2x2 cells
+    c = SparseDownConv3d(64, 128)(e, link)               # nn.Conv3d(k=2, s=2) on the fine voxels
+    u = SparseUpConv3d(128, 64)(c, link)                 # nn.ConvTranspose3d(k=2, s=2) back to them
+
+The down forward and the up input gradient are the 8-tap gather through link.child (the kernels
+above at taps = 8); the up forward and the down input gradient have one tap per output row and
+run pcs_sparse_conv_rows, which writes each row once from its own tap's GEMM tile.
 """
 from __future__ import annotations
 
@@ -37,6 +47,28 @@ PAIR_WGRAD = True
 PAIR_WGRAD_MAX_CH2 = 64 * 64
 
 
+def _build_pairs(nmap: torch.Tensor):
+    """Per-tap pair lists of an int32 [M, taps] map (pcs_sparse_pairs_*; one host read of the tap
+    counts): (pair_in, pair_out, pair_pos, tap_off, P) with tap_off a host int64 array of
+    taps + 1 entries."""
+    (M, taps), dev = nmap.shape, nmap.device
+    st = L.stream_ptr(dev)
+    nb = int(L.load().pcs_sparse_pairs_workspace(M, taps))
+    if nb < 0:
+        raise L.PcsError(L.load().pcs_last_error().decode())
+    ws = torch.empty(max(nb // 4, 1), dtype=torch.int32, device=dev)
+    counts = torch.empty(taps, dtype=torch.int64, device=dev)
+    L.call("pcs_sparse_pairs_count", L.ptr(nmap), M, taps, L.ptr(ws), L.ptr(counts), st)
+    tap_off = (ct.c_int64 * (taps + 1))(0, *torch.cumsum(counts, 0).tolist())
+    P = int(tap_off[taps])
+    pin = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    pout = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+    ppos = torch.empty(M, taps, dtype=torch.int32, device=dev)
+    L.call("pcs_sparse_pairs_build", L.ptr(nmap), M, taps, L.ptr(ws), L.ptr(counts), L.ptr(pin), L.ptr(pout),
+           L.ptr(ppos), st)
+    return pin, pout, ppos, tap_off, P
+
+
 @dataclass
 class SparseVoxels:
     keys: torch.Tensor         # int64 [V] (u64 keys: scene * G^3 + (ix * G + iy) * G + iz), ascending
@@ -55,22 +87,7 @@ class SparseVoxels:
         the 27 tap counts): (pair_in, pair_out, pair_pos, tap_off, P) with tap_off a host int64
         array of 28 entries."""
         if self._pairs is None:
-            V, dev = self.num_voxels, self.nbr.device
-            st = L.stream_ptr(dev)
-            nb = int(L.load().pcs_sparse_pairs_workspace(V, TAPS))
-            if nb < 0:
-                raise L.PcsError(L.load().pcs_last_error().decode())
-            ws = torch.empty(max(nb // 4, 1), dtype=torch.int32, device=dev)
-            counts = torch.empty(TAPS, dtype=torch.int64, device=dev)
-            L.call("pcs_sparse_pairs_count", L.ptr(self.nbr), V, TAPS, L.ptr(ws), L.ptr(counts), st)
-            tap_off = (ct.c_int64 * (TAPS + 1))(0, *torch.cumsum(counts, 0).tolist())
-            P = int(tap_off[TAPS])
-            pin = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
-            pout = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
-            ppos = torch.empty(V, TAPS, dtype=torch.int32, device=dev)
-            L.call("pcs_sparse_pairs_build", L.ptr(self.nbr), V, TAPS, L.ptr(ws), L.ptr(counts), L.ptr(pin), L.ptr(pout),
-                   L.ptr(ppos), st)
-            self._pairs = (pin, pout, ppos, tap_off, P)
+            self._pairs = _build_pairs(self.nbr)
         return self._pairs
 
     def use_pairs(self) -> bool:
@@ -237,4 +254,219 @@ class SubMConv3d(torch.nn.Module):
         return submanifold_conv3d(x, self.weight, sv, self.bias, out_dtype)
 
 
-__all__ = ["CH_ALIGN", "SparseVoxels", "SubMConv3d", "sparse_from_keys", "sparse_voxels", "submanifold_conv3d"]
+# ---- stride-2 down / up convolutions (k = 2, s = 2) between a fine level and its coarse level
+K2_TAPS = 8
+
+
+@dataclass
+class CoarseLink:
+    """The maps between the voxels of a level (grid G, even) and of its coarse level (G / 2): a
+    coarse voxel is a 2x2x2 cell with at least one occupied fine voxel; tap = ((ix & 1) * 2 +
+    (iy & 1)) * 2 + (iz & 1) is a fine voxel's corner of its cell (the tap order of a torch
+    Conv3d weight [Cout, Cin, 2, 2, 2])."""
+    child: torch.Tensor    # int32 [Vc, 8]: row of the fine voxel at tap t of the cell, or -1
+    parent: torch.Tensor   # int32 [Vf]: row of the coarse voxel
+    tap: torch.Tensor      # int32 [Vf]
+    up: torch.Tensor       # int32 [Vf, 8]: parent[f] at column tap[f], -1 elsewhere
+    fine: int
+    coarse: int
+    _down: tuple = field(default=None, repr=False)
+    _up: tuple = field(default=None, repr=False)
+
+    def down_pairs(self):
+        """Pair lists of the child map (in: fine row, out: coarse row), as SparseVoxels.pairs()."""
+        if self._down is None:
+            self._down = _build_pairs(self.child)
+        return self._down
+
+    def up_pairs(self):
+        """Pair lists of the up map (in: coarse row, out: fine row; every fine row once)."""
+        if self._up is None:
+            self._up = _build_pairs(self.up)
+        return self._up
+
+    def use_pairs(self) -> bool:
+        """The form of the 8-tap gather through the child map (the pair lists or the tile gather):
+        SparseVoxels.use_pairs()'s rule; the child map has one entry per fine voxel."""
+        return self.coarse > 0 and self.fine <= PAIR_TAPS_MAX * self.coarse
+
+
+def coarsen(sv: SparseVoxels):
+    """(sv_coarse, link): the coarse level of sv (grid / 2; its voxels are the occupied 2x2x2
+    cells, rows in ascending key order as sparse_from_keys documents, with their own hash table and
+    27-neighbour map) and the CoarseLink between the two.  sv.grid must be even."""
+    if sv.grid % 2 != 0:
+        raise ValueError(f"coarsen: the grid must be even, got {sv.grid}")
+    V, dev = sv.num_voxels, sv.keys.device
+    st = L.stream_ptr(dev)
+    pkey = torch.empty(V, dtype=torch.int64, device=dev)
+    tap = torch.empty(V, dtype=torch.int32, device=dev)
+    L.call("pcs_sparse_coarse_keys", L.ptr(sv.keys), V, sv.grid, L.ptr(pkey), L.ptr(tap), st)
+    ckeys, crow = torch.unique(pkey, sorted=True, return_inverse=True)
+    svc = sparse_from_keys(ckeys, sv.grid // 2)
+    Vc = svc.num_voxels
+    child = torch.empty(Vc, K2_TAPS, dtype=torch.int32, device=dev)
+    parent = torch.empty(V, dtype=torch.int32, device=dev)
+    up = torch.empty(V, K2_TAPS, dtype=torch.int32, device=dev)
+    crow = crow.to(torch.int64).contiguous()
+    L.call("pcs_sparse_coarse_maps", L.ptr(crow), L.ptr(tap), V, Vc, L.ptr(child), L.ptr(parent), L.ptr(up), st)
+    return svc, CoarseLink(child, parent, tap, up, V, Vc)
+
+
+def _conv_rows(link, x, cin, w, cout, bias, y, ydt):
+    """y[f] = b + W[tap[f]] x[parent[f]]: one tap per output row (pcs_sparse_conv_rows)."""
+    pin, pout, _, tap_off, P = link.up_pairs()
+    assert P == link.fine, "the up map has one pair per fine voxel"
+    L.call("pcs_sparse_conv_rows", L.ptr(pin), L.ptr(pout), ct.addressof(tap_off), K2_TAPS, link.fine, L.ptr(x), cin,
+           L.ptr(w), cout, L.ptr(bias) if bias is not None else None, L.ptr(y), ydt, L.stream_ptr(x.device))
+
+
+def _conv_cells(link, x, cin, w, cout, bias, y, ydt):
+    """y[m] = b + sum_t W[t] x[child[m][t]]: the 8-tap gather, through the pair lists or in tiles."""
+    st = L.stream_ptr(x.device)
+    if link.use_pairs():
+        pin, _, ppos, tap_off, P = link.down_pairs()
+        z = torch.empty(max(P, 1), cout, dtype=torch.float32, device=x.device)
+        L.call("pcs_sparse_conv_pairs", L.ptr(pin), L.ptr(ppos), ct.addressof(tap_off), K2_TAPS, link.coarse, L.ptr(x),
+               cin, L.ptr(w), cout, L.ptr(bias) if bias is not None else None, L.ptr(z), L.ptr(y), ydt, 0, st)
+    else:
+        L.call("pcs_sparse_conv", L.ptr(link.child), link.coarse, K2_TAPS, L.ptr(x), cin, L.ptr(w), cout,
+               L.ptr(bias) if bias is not None else None, L.ptr(y), ydt, 0, st)
+
+
+class _StrideConvFn(torch.autograd.Function):
+    """Both k = 2, s = 2 layers, w in kernel layout [Cout, 8 * Cin] (fp32 master), channel counts
+    off the 64 multiple zero-padded (exact, as _SubMConvFn).
+      down: y_c[m] = b + sum_t W_t x_f[child[m][t]];  dx_f[f] = W_tap(f)^T dy[parent[f]]
+      up:   y_f[f] = b + W_tap(f) x_c[parent[f]];     dx_c[m] = sum_t W_t^T dy[child[m][t]]
+    The weight gradient sums dy[out] (x) x[in] over the pairs of the forward's map."""
+
+    @staticmethod
+    def forward(ctx, x, wk, bias, link, up, out_dtype):
+        if not x.is_cuda:
+            raise RuntimeError("pcs_amd sparse conv runs on a HIP device only (no CPU fallback)")
+        rows_in, rows_out = (link.coarse, link.fine) if up else (link.fine, link.coarse)
+        if x.dtype != torch.bfloat16 or x.dim() != 2 or x.shape[0] != rows_in:
+            raise ValueError(f"x must be bf16 [{rows_in}, C]: the {'coarse' if up else 'fine'} voxels of the link")
+        cin, cout = x.shape[1], wk.shape[0]
+        if wk.shape[1] != K2_TAPS * cin:
+            raise ValueError(f"weight has {wk.shape[1] // K2_TAPS} input channels, x has {cin}")
+        cin_k, cout_k = _ceil(cin), _ceil(cout)
+        xk = _pad_channels(x, cin_k)
+        if (cin_k, cout_k) != (cin, cout):
+            wp = wk.new_zeros(cout_k, K2_TAPS, cin_k)
+            wp[:cout, :, :cin] = wk.reshape(cout, K2_TAPS, cin)
+            wk = wp.reshape(cout_k, K2_TAPS * cin_k)
+        wb = _bf16_2d(wk, cout_k, K2_TAPS * cin_k)
+        bk = None
+        if bias is not None:
+            bk = bias.float().contiguous() if cout_k == cout else _pad_channels(bias.float(), cout_k)
+        y = torch.empty(rows_out, cout_k, dtype=out_dtype, device=x.device)
+        ydt = L.BF16 if out_dtype == torch.bfloat16 else L.F32
+        (_conv_rows if up else _conv_cells)(link, xk, cin_k, wb, cout_k, bk, y, ydt)
+        ctx.save_for_backward(xk, wb)
+        ctx.link, ctx.up = link, up
+        # the up map's tile-gather weight gradient would run 8 taps for the one each row has: the
+        # up layer takes the pair lists at every width
+        ctx.wpairs = up or (PAIR_WGRAD and cin_k * cout_k <= PAIR_WGRAD_MAX_CH2)
+        ctx.cfg = (bias is not None, cin, cout)
+        return y if cout_k == cout else y[:, :cout].contiguous()
+
+    @staticmethod
+    def backward(ctx, dy):
+        xk, wb = ctx.saved_tensors
+        link, up = ctx.link, ctx.up
+        has_bias, cin, cout = ctx.cfg
+        rows_in, cin_k = xk.shape
+        rows_out = link.fine if up else link.coarse
+        cout_k = wb.shape[0]
+        dev, st = xk.device, L.stream_ptr(xk.device)
+        dyb = _bf16_2d(_pad_channels(dy, cout_k), rows_out, cout_k)
+        dx = dwk = db = None
+        if ctx.needs_input_grad[0]:
+            wt = torch.empty(cin_k, K2_TAPS * cout_k, dtype=torch.bfloat16, device=dev)
+            L.call("pcs_conv3d_weight_t", L.ptr(wb), cout_k, K2_TAPS, cin_k, L.ptr(wt), st)
+            dx = torch.empty(rows_in, cin_k, dtype=torch.bfloat16, device=dev)
+            (_conv_cells if up else _conv_rows)(link, dyb, cout_k, wt, cin_k, None, dx, L.BF16)
+            if cin_k != cin:
+                dx = dx[:, :cin].contiguous()
+        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
+            nmap = link.up if up else link.child
+            if ctx.wpairs:
+                pin, pout, _, tap_off, _ = link.up_pairs() if up else link.down_pairs()
+                nbytes = int(L.load().pcs_sparse_conv_wgrad_pairs_workspace(ct.addressof(tap_off), K2_TAPS, rows_out,
+                                                                            cin_k, cout_k))
+            else:
+                nbytes = int(L.load().pcs_sparse_conv_wgrad_workspace(rows_out, K2_TAPS, cin_k, cout_k))
+            if nbytes < 0:
+                raise L.PcsError(L.load().pcs_last_error().decode())
+            ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
+            dwk = torch.empty(cout_k, K2_TAPS * cin_k, dtype=torch.float32, device=dev)
+            db = torch.empty(cout_k, dtype=torch.float32, device=dev) if has_bias else None
+            if ctx.wpairs:
+                L.call("pcs_sparse_conv_wgrad_pairs", L.ptr(pin), L.ptr(pout), ct.addressof(tap_off), K2_TAPS, rows_out,
+                       L.ptr(xk), cin_k, L.ptr(dyb), cout_k, L.ptr(ws), nbytes, L.ptr(dwk), L.ptr(db), st)
+            else:
+                L.call("pcs_sparse_conv_wgrad", L.ptr(nmap), rows_out, K2_TAPS, L.ptr(xk), cin_k, L.ptr(dyb), cout_k,
+                       L.ptr(ws), nbytes, L.ptr(dwk), L.ptr(db), st)
+            if (cin_k, cout_k) != (cin, cout):
+                dwk = dwk.reshape(cout_k, K2_TAPS, cin_k)[:cout, :, :cin].reshape(cout, K2_TAPS * cin)
+                db = db[:cout] if db is not None else None
+        return dx, dwk, db, None, None, None
+
+
+def sparse_conv3d_down(x_fine, weight, link: CoarseLink, bias=None, out_dtype=torch.bfloat16):
+    """k = 2, s = 2 convolution from the fine voxels of link to its coarse voxels: x_fine bf16
+    [Vf, Cin], weight [Cout, Cin, 2, 2, 2] (torch Conv3d layout, fp32), bias [Cout] or None; returns
+    [Vc, Cout].  On a dense grid that is zero off the occupied fine voxels, the output at the
+    coarse voxels equals Conv3d(k=2, s=2)'s there; every other coarse site would hold the bias
+    alone and is not represented."""
+    cout, cin = weight.shape[0], weight.shape[1]
+    if tuple(weight.shape[2:]) != (2, 2, 2):
+        raise ValueError("sparse_conv3d_down is the 2x2x2, stride-2 form")
+    wk = weight.permute(0, 2, 3, 4, 1).reshape(cout, K2_TAPS * cin)
+    return _StrideConvFn.apply(x_fine, wk, bias, link, False, out_dtype)
+
+
+def sparse_conv_transpose3d_up(x_coarse, weight, link: CoarseLink, bias=None, out_dtype=torch.bfloat16):
+    """k = 2, s = 2 transposed convolution from the coarse voxels of link back to its fine voxels:
+    x_coarse bf16 [Vc, Cin], weight [Cin, Cout, 2, 2, 2] (torch ConvTranspose3d layout, fp32), bias
+    [Cout] or None; returns [Vf, Cout].  On a dense coarse grid that is zero off the coarse voxels,
+    the output at the fine occupied voxels equals ConvTranspose3d(k=2, s=2)'s there.  It takes the
+    link of the encoder (an inverse convolution): the decoder returns to exactly the encoder's
+    voxel set, the other fine sites of an occupied cell are not represented."""
+    cin, cout = weight.shape[0], weight.shape[1]
+    if tuple(weight.shape[2:]) != (2, 2, 2):
+        raise ValueError("sparse_conv_transpose3d_up is the 2x2x2, stride-2 form")
+    wk = weight.permute(1, 2, 3, 4, 0).reshape(cout, K2_TAPS * cin)
+    return _StrideConvFn.apply(x_coarse, wk, bias, link, True, out_dtype)
+
+
+class SparseDownConv3d(torch.nn.Module):
+    """sparse_conv3d_down with nn.Conv3d(cin, cout, 2, 2)'s parameter layout and init."""
+
+    def __init__(self, cin, cout, bias=True):
+        super().__init__()
+        ref = torch.nn.Conv3d(cin, cout, 2, 2, bias=bias)
+        self.weight, self.bias = ref.weight, ref.bias
+
+    def forward(self, x, link: CoarseLink, out_dtype=torch.bfloat16):
+        return sparse_conv3d_down(x, self.weight, link, self.bias, out_dtype)
+
+
+class SparseUpConv3d(torch.nn.Module):
+    """sparse_conv_transpose3d_up with nn.ConvTranspose3d(cin, cout, 2, 2)'s parameter layout and
+    init."""
+
+    def __init__(self, cin, cout, bias=True):
+        super().__init__()
+        ref = torch.nn.ConvTranspose3d(cin, cout, 2, 2, bias=bias)
+        self.weight, self.bias = ref.weight, ref.bias
+
+    def forward(self, x, link: CoarseLink, out_dtype=torch.bfloat16):
+        return sparse_conv_transpose3d_up(x, self.weight, link, self.bias, out_dtype)
+
+
+__all__ = ["CH_ALIGN", "CoarseLink", "SparseDownConv3d", "SparseUpConv3d", "SparseVoxels", "SubMConv3d", "coarsen",
+           "sparse_conv3d_down", "sparse_conv_transpose3d_up", "sparse_from_keys", "sparse_voxels",
+           "submanifold_conv3d"]
