@@ -789,7 +789,35 @@ int pcs_sparse_conv_wgrad_pairs(const int32_t *pair_in, const int32_t *pair_out,
                                 int32_t taps, int64_t M, const void *X, int32_t Cin, const void *dY, int32_t Cout,
                                 void *workspace, int64_t workspace_bytes, float *dW, float *db, pcs_stream_t stream);
 
-/* Build-time identification and error string.  pcs_abi_version() returns PCS_ABI_VERSION,
+/*
+ * Point <-> voxel transfer on the occupied-voxel path (csrc/pointvoxel.hip; build-defined, the
+ * numpy statement is tests/point_voxel_refs.py): what connects per-point features to any level of
+ * the sparse pyramid, forward and backward, without atomics.
+ * pcs_trilinear_index: for each point p (points [T][4] f32, CSR offsets [num_scenes + 1], the box
+ *   and grid of the level, its hash table) with u_d = ((p_d - lo_d) / (hi_d - lo_d)) * grid in f32:
+ *   own [T] i32 = row of the voxel clamp(floor(u), 0, grid - 1) or -1; corner [T][8] i32 and
+ *   weight [T][8] f32 = the eight voxels b + a around c_d = min(max(u_d, 0), grid) - 0.5 (b =
+ *   floor(c), f = c - b, k = (ax * 2 + ay) * 2 + az; -1 outside the grid or unoccupied) with
+ *   prod_d (a_d ? f_d : 1 - f_d) divided by its sum over the present corners (0 where missing, all
+ *   0 when none is present).
+ * pcs_rows_interp: Y[m] = sum_{k < K} w[m][k] * X[idx[m][k]], 1 <= K <= 8; idx [M][K] i32 (-1
+ *   skipped), w [M][K] f32 or NULL (= 1); X [*, C], Y [M, C], each PCS_F32 or PCS_BF16, fp32
+ *   accumulation in k order.  C % 8 == 0 when either side is bf16, else C % 4 == 0.
+ * pcs_rows_segsum: Y[m] = scale[m] * sum_{j in [seg_off[m], seg_off[m + 1])} w[j] * X[src[j]] in
+ *   ascending j; seg_off [M + 1] i64 on the DEVICE, src i32 (-1 skipped), w and scale f32 or NULL
+ *   (= 1); dtypes and C as pcs_rows_interp.  An empty segment stores a zero row.
+ * Every output row is stored exactly once; M == 0 / T == 0 return 0 without a launch.
+ */
+int pcs_trilinear_index(const float *points, const int64_t *offsets, int64_t num_scenes, int64_t T, int32_t grid,
+                        float lo_x, float lo_y, float lo_z, float hi_x, float hi_y, float hi_z,
+                        const uint64_t *table_keys, const int32_t *table_vals, int64_t capacity, int32_t *own,
+                        int32_t *corner, float *weight, pcs_stream_t stream);
+int pcs_rows_interp(const void *X, int32_t xdtype, const int32_t *idx, const float *w, int64_t M, int32_t K,
+                    int32_t C, void *Y, int32_t ydtype, pcs_stream_t stream);
+int pcs_rows_segsum(const void *X, int32_t xdtype, const int32_t *src, const float *w, const int64_t *seg_off,
+                    const float *scale, int64_t M, int32_t C, void *Y, int32_t ydtype, pcs_stream_t stream);
+
+/* Build-time identification and error string. pcs_abi_version() returns PCS_ABI_VERSION,
  * bumped with every change to an argument struct's layout or an entry point's signature
  * (2: pcs_gemm_args gained `gram`, the w4 entry points were removed); a binding checks it
  * before its first call. */

@@ -29,6 +29,9 @@ _LAZY = {
     "DevicePrefetcher": ("loader", "DevicePrefetcher"),
     "voxelize": ("voxel", "voxelize"),
     "voxel_ids": ("voxel", "voxel_ids"),
+    "point_voxel_map": ("pointvoxel", "point_voxel_map"),
+    "voxel_mean": ("pointvoxel", "voxel_mean"),
+    "devoxelize": ("pointvoxel", "devoxelize"),
 }
 
 

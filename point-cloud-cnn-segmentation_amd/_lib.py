@@ -160,6 +160,10 @@ SIGNATURES = [
     ("pcs_voxel_hash_build", ct.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
     ("pcs_voxel_hash_find", ct.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
     ("pcs_sparse_neighbors", ct.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp]),
+    ("pcs_trilinear_index", ct.c_int, [_vp, _vp, _i64, _i64, _i32, _f, _f, _f, _f, _f, _f, _vp, _vp, _i64, _vp, _vp,
+                                       _vp, _vp]),
+    ("pcs_rows_interp", ct.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp]),
+    ("pcs_rows_segsum", ct.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp]),
     ("pcs_gram_workspace", _i64, [_i64, _i64, _i32, _i32, ct.POINTER(_i32)]),
     ("pcs_gram", ct.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     ("pcs_pool_rows_add", ct.c_int, [_vp, _i32, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32,

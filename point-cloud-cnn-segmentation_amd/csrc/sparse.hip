@@ -14,20 +14,15 @@
 //   coarse level the occupied 2x2x2 cells of an even grid (key of the cell on the G / 2 grid) and
 //                the child / parent / up maps of a k = 2, s = 2 convolution between the levels
 #include "common.h"
+#include "voxel_hash.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr uint64_t EMPTY = ~0ull;
+using pcs_hash::EMPTY;
+using pcs_hash::hash_find;
+using pcs_hash::mix64;
 
-PCS_DEV uint64_t mix64(uint64_t k) {   // splitmix64 finaliser
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
-}
+constexpr int THREADS = 256;
 
 PCS_DEV int64_t voxel_of(const float *p, int G, const float *lo, const float *hi) {
   int64_t id = 0;
@@ -85,17 +80,6 @@ __global__ __launch_bounds__(THREADS) void hash_insert_kernel(const uint64_t *__
       h = (h + 1) & mask;
     }
   }
-}
-
-PCS_DEV int32_t hash_find(const uint64_t *__restrict__ tk, const int32_t *__restrict__ tv, uint64_t mask, uint64_t k) {
-  uint64_t h = mix64(k) & mask;
-  for (uint64_t probe = 0; probe <= mask; ++probe) {
-    const uint64_t s = tk[h];
-    if (s == k) return tv[h];
-    if (s == EMPTY) return -1;
-    h = (h + 1) & mask;
-  }
-  return -1;
 }
 
 __global__ __launch_bounds__(THREADS) void hash_find_kernel(const uint64_t *__restrict__ tk, const int32_t *__restrict__ tv,
