@@ -112,7 +112,9 @@ PCS_DEV uint32_t mask_bits(const uint8_t *__restrict__ bits, int64_t row, int K,
 // s_barrier.  Unlike __syncthreads() (a workgroup-scope fence) it never waits on vmcnt, so
 // global loads issued for a later pipeline stage stay in flight across it (spill stores
 // would otherwise make the fence drain them).  One asm statement with a "memory" clobber:
-// the compiler moves no memory access across it.
+// the compiler moves no memory access across it.  It may still move MFMAs and other non-memory
+// instructions: a kernel with a hand-placed instruction order takes kernel_prims.h's
+// barrier_lds(), the same statement between two sched_barriers.
 PCS_DEV void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // wave-level helpers (wave64)

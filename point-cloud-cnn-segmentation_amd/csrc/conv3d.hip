@@ -19,7 +19,7 @@
 // conv3d_wgrad_kernel: dW_t = dY^T X_t over output voxels in 32-voxel k-steps, both operands
 // staged row-major and read transposed (ds_read_b64_tr_b16) so the MFMA's k runs over voxels;
 // split over voxel slices with fp32 partials summed in a fixed order (deterministic).
-#include "common.h"
+#include "kernel_prims.h"
 
 namespace {
 
@@ -396,10 +396,6 @@ __global__ __launch_bounds__(THREADS) void stencil3_kernel(pcs_conv3d_geom g, co
 constexpr int WV = 32;   // voxels per k-step
 constexpr int WIMG = WV * 128;   // one [32][64] bf16 image
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 // 16-B chunk swizzle of image row r (even values: a 32-B pair of chunks stays adjacent): the
 // eight rows a 32-lane half reads (8g + 4h + q, two groups) land on distinct 32-B bank slots
 PCS_DEV int wsw(int r) { return 2 * (((r >> 1) & 1) | ((r >> 2) & 2)); }
@@ -409,10 +405,7 @@ PCS_DEV int woff(int r, int byte) { return r * 128 + ((((byte >> 4) ^ wsw(r)) <<
 PCS_DEV bf16x8 wfrag(const char *img, int cb, int lane) {
   const int g = lane >> 4, i = lane & 15;
   const int byte = (cb + 4 * (i & 3)) * 2;   // this lane supplies row 8g (+4) + i/4, columns cb + 4 (i%4)
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(img + woff(8 * g + (i >> 2), byte)));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(img + woff(8 * g + 4 + (i >> 2), byte)));
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
+  return tr_frag2(img + woff(8 * g + (i >> 2), byte), img + woff(8 * g + 4 + (i >> 2), byte));
 }
 
 // One workgroup covers the dx taps of one (dz, dy) (all k of them, sharing the dY image; one tap

@@ -18,7 +18,7 @@
 // wgrad: wave w owns output channels 64*w.. x all 64 inputs (16 accumulators, K = 64 rows).
 // The dy tile is a [m][col] image (rows permuted as pcs_wgrad's bf16 tiles, 32-B padding)
 // read with ds_read_b128 for the dgrad operand and ds_read_b64_tr_b16 for the wgrad one.
-#include "common.h"
+#include "kernel_prims.h"
 
 namespace {
 
@@ -47,31 +47,12 @@ constexpr int DY_CPR = COUT / 8, DY_RP = THREADS / DY_CPR, DY_NCH = MS / DY_RP; 
 constexpr int X_CPR = CIN / 8, X_RP = THREADS / X_CPR;                            // 8, 64
 static_assert(X_RP == MS, "one x chunk per thread");
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-PCS_DEV int prow(int r) { return (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1); }
 // (slot ^ (c & 15): the dgrad's 16-B fragment reads of 16 rows c at slots 4 kk + g fall in 16
 // different slots of a 64-slot row; with c & 7 the two lane groups g met in the same 8, 2-way)
 PCS_DEV int wt_off(int c, int slot) { return c * WT_ROWB + ((slot ^ (c & 15)) << 4); }
 
-PCS_DEV void lds_vec8(const float *p, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4 *>(p);
-  const float4 b = *reinterpret_cast<const float4 *>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
 PCS_DEV bf16x8 tr_read(const char *base, int r0, int r1, int rowb, int col) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(base + r0 * rowb + col * 2));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(base + r1 * rowb + col * 2));
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
+  return tr_frag2(base + r0 * rowb + col * 2, base + r1 * rowb + col * 2);
 }
 
 // FOLDED (dy_mode RAW): dy is dZ itself and Wt = (diag(alpha) W_l)^T, so the same contractions
@@ -509,9 +490,6 @@ template <int COUT, int CIN, int CB, int MS, bool MASK, bool ADD> struct FB {
   static constexpr int NCH_D = MS * COUT / 8 / THREADS, NCH_P = MS * CB / 8 / THREADS;
   static_assert(NCH_D >= 1 && NCH_P >= 1 && MS % 32 == 0, "staging");
 };
-
-PCS_DEV float bf_lo(uint32_t u) { return __uint_as_float(u << 16); }
-PCS_DEV float bf_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 
 // (the 64-wide layers run two workgroups per CU: at most 128 VGPRs)
 template <int COUT, int CIN, int CB, int MS, bool MASK, bool ADD>

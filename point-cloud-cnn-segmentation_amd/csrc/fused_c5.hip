@@ -16,7 +16,7 @@
 //   y4 of the step for bn4's ReLU mask and S2.
 // dz5 rows carry the chunk permutation ftr of the r03 fused_seg.hip, now in git history (conflict-free fragment reads), y4
 // rows the (row & 15) permutation (conflict-free epilogue reads), both put on the DMA source.
-#include "common.h"
+#include "kernel_prims.h"
 
 namespace {
 
@@ -36,38 +36,9 @@ static_assert(BYTES <= 160 * 1024, "LDS budget");
 constexpr int KS1 = K1 / 32, KS2 = K2 / 32;  // MFMA k-steps
 constexpr int DZP = DZB / 1024;             // 64 pieces: 8 per wave
 
-typedef __attribute__((address_space(3))) void lds_void_t;
+PCS_DEV int fyp(int row) { return row & 15; }   // slot permutation of the y4 rows
 
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-PCS_DEV int ftr(int row) { return ((row & 3) << 1) | (row & 8); }
-PCS_DEV int fyp(int row) { return row & 15; }
-
-template <int OFF> PCS_DEV void glds16o(const char *sbase, uint32_t voff, uint32_t m0base) {
-  asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(m0base), "n"(OFF) : "memory", "scc");
-}
-PCS_DEV uint32_t m0_save() {
-  uint32_t k;
-  asm volatile("s_mov_b32 %0, m0" : "=s"(k));
-  return k;
-}
-PCS_DEV void m0_restore(uint32_t k) { asm volatile("s_mov_b32 m0, %0" ::"s"(k)); }
-template <int N> PCS_DEV void wait_vm() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-PCS_DEV void barrier_lds() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-PCS_DEV float bf_lo(uint32_t u) { return __uint_as_float(u << 16); }
-PCS_DEV float bf_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
-PCS_DEV int split_idx(int i, int n) { return ((i & 7) >> 2) * (n / 2) + (i >> 3) * 4 + (i & 3); }
+// 8 coefficients in the split layout (split_idx): this file's own overload of lds_vec8
 PCS_DEV void lds_vec8(const char *p, int half_bytes, float (&v)[8]) {
   const u32x4 x = *reinterpret_cast<const u32x4 *>(p);
   const u32x4 y = *reinterpret_cast<const u32x4 *>(p + half_bytes);

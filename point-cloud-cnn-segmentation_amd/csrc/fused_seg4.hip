@@ -30,7 +30,7 @@
 //   conflict-free by the bank rule of MI355X_MICROARCH.md section LDS;
 // * Yp rows: chunk c at c ^ (r & 15) (16 rows at one column: 16 distinct slots);
 // * x tile of a wave: [16 rows][64 columns], 128-B rows, chunk c at c ^ (4 ((r >> 1) & 1)).
-#include "common.h"
+#include "kernel_prims.h"
 
 namespace {
 
@@ -66,15 +66,6 @@ template <int COUT> struct S4 {
   static constexpr bool DACC_V = true;   // input gradient D in VGPRs (see the k-step loop)
 };
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 // LDS-DMA through a buffer descriptor (su32x4 in SGPRs): rows past the descriptor's range
 // read as zeros (and are never used), so no row clamping and no per-step branches.  M0 is
 // set per piece and not restored: hipcc never reads M0 in this file's kernels
@@ -105,36 +96,11 @@ PCS_DEV su32x4 rsrc_of(const void *base, uint32_t bytes) {
   r.w = 0x00020000u;
   return r;
 }
-template <int N> PCS_DEV void wait_vm() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-PCS_DEV void barrier_lds() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-PCS_DEV void wait_lgkm0() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 PCS_DEV int fdz(int r) { return ((r & 3) << 2) | ((0x1320 >> (4 * ((r >> 2) & 3))) & 3); }
 PCS_DEV int fyp(int r) { return 2 * (r & 7); }
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-PCS_DEV bf16x8 tr_frag2(const char *p0, const char *p1) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)p1);
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-// split coefficient layout: elements 0-3 of every chunk first, then elements 4-7
-PCS_DEV int split_idx(int i, int n) { return ((i & 7) >> 2) * (n / 2) + (i >> 3) * 4 + (i & 3); }
-PCS_DEV float bf_lo(uint32_t u) { return __uint_as_float(u << 16); }
-PCS_DEV float bf_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
 // the coefficients of 8 channels as 4 packed pairs (channels 2 i, 2 i + 1)
 PCS_DEV void lds_pairs8(const char *p, int half_bytes, f32x2 (&v)[4]) {
   const u32x4 x = *reinterpret_cast<const u32x4 *>(p);

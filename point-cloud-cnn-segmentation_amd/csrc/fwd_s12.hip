@@ -25,7 +25,7 @@
 // The 16-B slots of an LDS row hold the logical slots XOR-permuted by the row (y2 / a2 and W1
 // rows of 128 B: (row >> 1) & 7; x rows of 1 KB: row & 15), so the fragment reads are
 // bank-conflict free.
-#include "common.h"
+#include "kernel_prims.h"
 
 namespace {
 
@@ -62,37 +62,10 @@ constexpr int KS2 = K2 / 32;                  // stage-2 k-steps
 static_assert(NST == 3, "the ring's roles assume three stages");
 constexpr int VM_WAIT = 6;
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 template <int N> PCS_DEV float row_ror(float v) {   // rotate within the 16 lanes of a DPP row
   return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, true));
 }
 PCS_DEV int f64s(int r) { return (r >> 1) & 7; }   // slot permutation of 128-B rows
-
-template <int OFF> PCS_DEV void glds4o(const char *sbase, uint32_t voff, uint32_t m0base) {
-  asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(m0base), "n"(OFF) : "memory", "scc");
-}
-PCS_DEV uint32_t m0_save() {
-  uint32_t k;
-  asm volatile("s_mov_b32 %0, m0" : "=s"(k));
-  return k;
-}
-PCS_DEV void m0_restore(uint32_t k) { asm volatile("s_mov_b32 m0, %0" ::"s"(k)); }
-template <int N> PCS_DEV void wait_vm() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-PCS_DEV void barrier_lds() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 template <bool MASK>
 __global__ __launch_bounds__(THREADS) void fwd_s12_kernel(pcs_seg12_args a, int64_t rows_per_chunk) {

@@ -26,46 +26,11 @@
 // The 16-B slots of an LDS row hold the source chunks XOR-permuted by the row (put on the DMA
 // source address, since the DMA writes LDS linearly), so the B-fragment reads (16 rows, one
 // chunk) are bank-conflict free.
-#include "common.h"
+#include "kernel_prims.h"
 
 namespace {
 
 constexpr int THREADS = 512;
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-template <int OFF> PCS_DEV void glds16o(const char *sbase, uint32_t voff, uint32_t m0base) {
-  asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(m0base), "n"(OFF) : "memory", "scc");
-}
-template <int OFF> PCS_DEV void glds4o(const char *sbase, uint32_t voff, uint32_t m0base) {
-  asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(m0base), "n"(OFF) : "memory", "scc");
-}
-PCS_DEV uint32_t m0_save() {
-  uint32_t k;
-  asm volatile("s_mov_b32 %0, m0" : "=s"(k));
-  return k;
-}
-PCS_DEV void m0_restore(uint32_t k) { asm volatile("s_mov_b32 m0, %0" ::"s"(k)); }
-template <int N> PCS_DEV void wait_vm() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-PCS_DEV void barrier_lds() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 // Shapes (K = input channels, NCOLS = output channels) and their tiling:
 //   NB output columns per workgroup, WCN wave columns (8 / WCN wave rows), MS rows per step,

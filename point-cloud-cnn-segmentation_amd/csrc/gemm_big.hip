@@ -16,7 +16,7 @@
 //   S1/S2) and max-pool max/min+argmax are per-thread over 16 rows, merged per tile
 //   through LDS into running per-column accumulators and written once per chunk in the
 //   generic kernel's partial layout.
-#include "common.h"
+#include "kernel_prims.h"
 
 #ifndef PCS_DGRAD_BATCH
 #define PCS_DGRAD_BATCH 16  // DGRAD epilogue: rows of Yp (and mask / addend) loaded per batch (all 16)
@@ -49,17 +49,6 @@ template <int PRO, int EPI> struct Lay {
 };
 
 PCS_DEV int swz8(int row, int slot) { return slot ^ ((row >> 1) & 7); }
-
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-PCS_DEV void lds_vec8(const float *p, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4 *>(p);
-  const float4 b = *reinterpret_cast<const float4 *>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
 
 // Pipeline (one LDS double buffer, one register stage, one barrier per 64-deep k-step):
 //   compute(ks) from LDS[ks&1]  ->  transform + write the registers (k-step ks+1) into

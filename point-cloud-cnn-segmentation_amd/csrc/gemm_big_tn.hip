@@ -12,7 +12,7 @@
 // * Gram mode (DYMODE = PCS_PRO_BNRELU, pcs_gram): both operands are a = relu(Y*s + t) of
 //   the same activations, only the upper 256-tiles of the symmetric a^T a are computed,
 //   and the diagonal tiles also sum their x columns (sum_m a[m, k]).
-#include "common.h"
+#include "kernel_prims.h"
 
 namespace {
 
@@ -24,22 +24,8 @@ constexpr int STAGE = 2 * OPB;
 constexpr int COEF = 6 * 256 * 4;          // alpha|beta|gamma|argmax (Cout cols), s|t (Cin cols)
 constexpr int LDS_BYTES = 2 * STAGE + COEF;
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-PCS_DEV int prow(int r) { return (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1); }
-
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
 PCS_DEV bf16x8 tr_frag(const char *tile, int r0, int r1, int col) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(tile + r0 * ROWB + col * 2));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(tile + r1 * ROWB + col * 2));
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
+  return tr_frag2(tile + r0 * ROWB + col * 2, tile + r1 * ROWB + col * 2);
 }
 
 template <int DYMODE, bool MASK>

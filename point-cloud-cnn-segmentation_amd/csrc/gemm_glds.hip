@@ -27,7 +27,7 @@
 // * The pipeline runs across the row tiles of a workgroup's chunk without draining: the
 //   epilogue works on the accumulators (DPP row reductions, per-wave running statistics in
 //   LDS outside the staging area), so the next tile's first K-tiles load while it runs.
-#include "common.h"
+#include "kernel_prims.h"
 
 #include <type_traits>
 
@@ -51,39 +51,8 @@ static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
 enum { MODE_FWD = 0, MODE_DGRAD = 1 };
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-PCS_DEV void sbar() { __builtin_amdgcn_sched_barrier(0); }
-// One LDS-DMA piece: 64 lanes x 16 B from sbase + voff (per lane) to lds_dst + 16*lane.  Inline
-// asm (the §5.7 recipe) so that the compiler's own wait insertion neither drains these loads
-// before unrelated LDS reads nor spills their 64-bit addresses: the kernel counts them itself.
-PCS_DEV void glds16(const char *sbase, uint32_t voff, char *lds_dst) {
-  const uint32_t m0v = (uint32_t)(uintptr_t)(lds_void_t *)lds_dst;
-  // (M0 not restored: hipcc never reads M0 in this file's kernels -- tests/test_asm_audit.py)
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(m0v)
-               : "memory");
-}
-PCS_DEV void barrier_raw() {
-  sbar();
-  asm volatile("s_barrier" ::: "memory");
-  sbar();
-}
-template <int N> PCS_DEV void wait_vm() {
-  sbar();
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  sbar();
-}
-PCS_DEV void wait_lgkm0() {
-  sbar();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  sbar();
-}
+// The LDS-DMA pieces are kernel_prims.h's glds16: M0 is set per piece and not restored, as hipcc
+// never reads M0 in this file's kernels (tests/test_asm_audit.py checks the compiled code)
 
 // Butterfly over the 16 lanes of a DPP row (quad xor 1, quad xor 2, half-row mirror, row
 // mirror): every lane of the row ends with the row's result.
@@ -254,7 +223,6 @@ __global__ __launch_bounds__(THREADS) void gemm_glds_kernel(pcs_gemm_args a, int
   // ---- fragment reads (ds_read_b128 of the swizzled 16-B chunks): bf16 16x16x32 takes
   // chunk kk*4 + lg for k-step kk; fp8 16x16x128 takes chunks 2 lg, 2 lg + 1 (32 bytes)
   // bf16: two 4-dword fragments per (i) / (j), one per k-step; fp8: one 8-dword fragment
-  typedef int v8i __attribute__((ext_vector_type(8)));
   u32x4 af[4][2], bfr[4][2];
   v8i af8[4], bf8[4];
   auto frag8 = [&](const char *p0, const char *p1) {

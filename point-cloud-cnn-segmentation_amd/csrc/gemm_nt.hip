@@ -16,7 +16,7 @@
 //   makes the ds_read_b128 fragment reads bank-conflict free.
 // * A workgroup walks a scene-aligned chunk of row tiles for one column block; blocks
 //   that share a chunk are mapped onto one XCD (round-robin dispatch, speed only).
-#include "common.h"
+#include "kernel_prims.h"
 
 namespace {
 
@@ -50,12 +50,6 @@ template <> struct Mfma<float> {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
   }
 };
-
-// bijective XCD-grouping remap of the linear block id (cdna_hip_programming.md §5)
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 
 constexpr int KMAX = 1024;   // prologue coefficient arrays staged in LDS (K <= KMAX)
 

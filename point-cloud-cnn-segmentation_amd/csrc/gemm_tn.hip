@@ -13,25 +13,17 @@
 // transpose delivers 4 consecutive m of one column per lane) or ds_read_b32 (fp32 MFMA
 // 16x16x4).  bf16 rows are permuted (bits 2<->3 of m swapped) and padded by 32 B so the
 // eight rows one transposed read touches land on eight distinct bank groups.
-#include "common.h"
+#include "kernel_prims.h"
 
 namespace {
 
 constexpr int THREADS = 256;
 
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
 template <typename T> struct TnCfg;
 template <> struct TnCfg<bf16_t> {
   static constexpr int MS = 64;    // rows (reduction) per step: 2 MFMA k-iterations
   static constexpr int PADB = 32;  // row padding in bytes
-  static PCS_DEV int prow(int r) { return (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1); }
+  static PCS_DEV int prow(int r) { return ::prow(r); }
 };
 template <> struct TnCfg<float> {
   static constexpr int MS = 16;
@@ -209,12 +201,13 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_kernel(pcs_wgrad_args a, int
         const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
         const int r0 = TnCfg<T>::prow(32 * kk + 8 * g + q), r1 = TnCfg<T>::prow(32 * kk + 8 * g + 4 + q);
         bf16x8 xf[FN], yf[FM];
+        // (tr_frag2's two reads, spelled out: through the helper hipcc allocates this kernel's
+        // registers differently, and tools/asm_equal.py is what vouches for a refactor here)
 #pragma unroll
         for (int j = 0; j < FN; ++j) {
           const int c = wn * (TN / 2) + j * 16 + 4 * p;
           s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(tB + r0 * OB::ROWB + c * 2));
           s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(tB + r1 * OB::ROWB + c * 2));
-          typedef short s16x8 __attribute__((ext_vector_type(8)));
           s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
           xf[j] = __builtin_bit_cast(bf16x8, v);
         }
@@ -223,7 +216,6 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_kernel(pcs_wgrad_args a, int
           const int c = wm * (TM / 2) + i * 16 + 4 * p;
           s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(tA + r0 * OA::ROWB + c * 2));
           s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(tA + r1 * OA::ROWB + c * 2));
-          typedef short s16x8 __attribute__((ext_vector_type(8)));
           s16x8 v = {lo4[0], lo4[1], lo4[2], lo4[3], hi4[0], hi4[1], hi4[2], hi4[3]};
           yf[i] = __builtin_bit_cast(bf16x8, v);
         }

@@ -26,7 +26,7 @@
 //   bn5 + ReLU to the accumulators, rounds to the storage type, widens the stores with
 //   v_permlane16_swap (16 B bf16 / 8 B fp8 per lane) and keeps per-lane column sums across
 //   the chunk in registers (one 16-lane reduction per chunk, not per tile).
-#include "common.h"
+#include "kernel_prims.h"
 
 #include <type_traits>
 
@@ -47,29 +47,12 @@ constexpr int OFF_PRO = OFF_RED + 2 * BNW * 4;          // bn4 scale | shift [K]
 constexpr int LDS_BYTES = OFF_PRO + 2 * K * 4;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
 // 16-B slot s of LDS row r holds logical slot s ^ (r & 15): the 16 rows a 16-lane group of
 // ds_read_b128 touches at one logical slot land in 16 distinct slots (all 64 banks)
 PCS_DEV int swz(int r, int slot) { return slot ^ (r & 15); }
 
-PCS_DEV void glds16(const char *sbase, uint32_t voff, char *lds_dst) {
-  const uint32_t m0v = (uint32_t)(uintptr_t)(lds_void_t *)lds_dst;
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(sbase), "s"(m0v)
-               : "memory");
-}
-template <int N> PCS_DEV void wait_vm() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
+// (the LDS-DMA pieces are glds16_keep_m0: this file is not among the M0-audited ones of
+// tests/test_asm_audit.py, so hipcc's own code may rely on M0 here)
 // wait until at most n (rounded down to the ladder) vector-memory operations are outstanding
 PCS_DEV void wait_vm_dyn(int n) {
   if (n >= 24) wait_vm<24>();
@@ -81,16 +64,6 @@ PCS_DEV void wait_vm_dyn(int n) {
   else if (n >= 4) wait_vm<4>();
   else if (n >= 2) wait_vm<2>();
   else wait_vm<0>();
-}
-PCS_DEV void barrier_raw() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-PCS_DEV void lds_vec8(const float *p, float (&v)[8]) {
-  const float4 x = *reinterpret_cast<const float4 *>(p);
-  const float4 y = *reinterpret_cast<const float4 *>(p + 4);
-  v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w; v[4] = y.x; v[5] = y.y; v[6] = y.z; v[7] = y.w;
 }
 PCS_DEV float dpp_sum16(float v) {   // sum over the 16 lanes of a DPP row (every lane gets it)
   auto d = [](float x, auto ctrl) {
@@ -171,7 +144,7 @@ __global__ __launch_bounds__(THREADS) void wres_bnrelu_kernel(pcs_gemm_args a, i
 #pragma unroll
     for (int g = 0; g < PIECES; ++g) {
       const uint32_t r = (uint32_t)min(prow[g], valid - 1);   // rows past the scene: clamped
-      glds16(sb, r * (uint32_t)ROWB + poff[g], dst + (PIECES * wid + g) * 1024);
+      glds16_keep_m0(sb, r * (uint32_t)ROWB + poff[g], dst + (PIECES * wid + g) * 1024);
     }
     issued += PIECES;
     mark[t % NSTAGE] = issued;

@@ -29,7 +29,7 @@
 //   the 16-B granules of row r are XOR-swizzled by (r >> 1) & 7, so the 16 rows a half-wave
 //   reads fill all 64 banks.  Products of e4m3 values are exact in the fp32 accumulators: G is
 //   the Gram of the stored activation, as in bf16.
-#include "common.h"
+#include "kernel_prims.h"
 
 #ifndef GG_PRIO
 #define GG_PRIO 1   // base wave priority: above the dropout draw that shares its CUs (step -0.36 ms)
@@ -48,37 +48,7 @@ template <bool FP8> struct GCfg {
   static constexpr int ROWB = 128 * ESZ;      // region row: 128 columns
 };
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef int v2i __attribute__((ext_vector_type(2)));
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) v2i lds_v2i;
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-PCS_DEV void sbar() { __builtin_amdgcn_sched_barrier(0); }
-PCS_DEV void glds16(const char *sbase, uint32_t voff, char *lds_dst) {
-  const uint32_t m0v = (uint32_t)(uintptr_t)(lds_void_t *)lds_dst;
-  // (M0 not restored: hipcc never reads M0 in this file's kernels -- tests/test_asm_audit.py)
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(m0v)
-               : "memory");
-}
-PCS_DEV void barrier_raw() {
-  sbar();
-  asm volatile("s_barrier" ::: "memory");
-  sbar();
-}
-template <int N> PCS_DEV void wait_vm() {
-  sbar();
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  sbar();
-}
-PCS_DEV void wait_lgkm0() {
-  sbar();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  sbar();
-}
+// (glds16 leaves M0 clobbered: hipcc never reads M0 in this file's kernels -- tests/test_asm_audit.py)
 
 PCS_DEV int gsw(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }   // bf16: 32-B granule swizzle of row r
 PCS_DEV int gsw8(int r) { return (r >> 1) & 7; }                     // fp8: 16-B granule swizzle
@@ -105,15 +75,7 @@ PCS_DEV v8i tr_frag8(const char *region, int r0, int byte) {
   return v;
 }
 PCS_DEV bf16x8 tr_frag(const char *region, int r0, int r1, int byte) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(region + roff(r0, byte)));
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)(region + roff(r1, byte)));
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
+  return tr_frag2(region + roff(r0, byte), region + roff(r1, byte));
 }
 
 // Workgroup L = split * ntile + tile: steps [split * steps / nsplit, (split + 1) * steps / nsplit)

@@ -14,7 +14,7 @@
 //   register kernel; class weights in registers (no gathers in the loop);
 // * dz rows go out through a buffer descriptor limited to the chunk's rows (the hardware drops
 //   rows past it), so every wave issues the same stores every step.
-#include "common.h"
+#include "kernel_prims.h"
 
 namespace {
 
@@ -38,28 +38,6 @@ static_assert(BYTES <= 160 * 1024, "LDS budget");
 constexpr int LPS = 3;                 // DMAs per wave per step: two y pieces, one label piece
 constexpr int SPS = 2;                 // output stores per wave per step
 static_assert((NST - 1) * (LPS + SPS) < 64, "vmcnt range");
-
-typedef __attribute__((address_space(3))) void lds_void_t;
-
-template <int OFF> PCS_DEV void glds16o(const char *sbase, uint32_t voff, uint32_t m0base) {
-  asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(m0base), "n"(OFF) : "memory", "scc");
-}
-template <int OFF> PCS_DEV void glds4o(const char *sbase, uint32_t voff, uint32_t m0base) {
-  asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(m0base), "n"(OFF) : "memory", "scc");
-}
-PCS_DEV uint32_t m0_save() {
-  uint32_t k;
-  asm volatile("s_mov_b32 %0, m0" : "=s"(k));
-  return k;
-}
-PCS_DEV void m0_restore(uint32_t k) { asm volatile("s_mov_b32 m0, %0" ::"s"(k)); }
-template <int N> PCS_DEV void wait_vm() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 
 template <int C>
 __global__ __launch_bounds__(THREADS, (C <= 2 ? HS_WPS : 1)) void head_stream_kernel(pcs_head_args a, int64_t rows_per_chunk) {

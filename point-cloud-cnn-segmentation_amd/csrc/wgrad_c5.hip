@@ -12,7 +12,7 @@
 //   blocks of a slice repeat this 128-wide transform, on one XCD, through L2);
 // * MFMA operands by ds_read_b64_tr_b16 of the row-major dz5 and x tiles (k = rows), the
 //   layouts (slot permutations, padded x rows) of the r03 fused_seg.hip, now in git history: bank-conflict free.
-#include "common.h"
+#include "kernel_prims.h"
 
 namespace {
 
@@ -44,45 +44,8 @@ constexpr int DZP = DZB / 1024 / 8;   // dz5 pieces per wave per step (2)
 constexpr int LPS = DZP + 1;          // + one y4 piece
 constexpr int OBW = NB / 128;         // 16-column output tiles of dz5 per wave (2)
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-PCS_DEV int xcd_remap(int bid, int nb) {
-  const int q = nb >> 3, r = nb & 7, x = bid & 7;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-}
-template <int OFF> PCS_DEV void glds16o(const char *sbase, uint32_t voff, uint32_t m0base) {
-  asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               :: "v"(voff), "s"(sbase), "s"(m0base), "n"(OFF) : "memory", "scc");
-}
-PCS_DEV uint32_t m0_save() {
-  uint32_t k;
-  asm volatile("s_mov_b32 %0, m0" : "=s"(k));
-  return k;
-}
-PCS_DEV void m0_restore(uint32_t k) { asm volatile("s_mov_b32 m0, %0" ::"s"(k)); }
-template <int N> PCS_DEV void wait_vm() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-PCS_DEV void barrier_lds() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 // slot permutations (the r03 fused_seg.hip, now in git history): dz5 rows chunk c at c ^ ftr(r); y4 rows at c ^ (r & 15);
-// x rows permuted (bits 2 <-> 3) and padded
-PCS_DEV int ftr(int row) { return ((row & 3) << 1) | (row & 8); }
-PCS_DEV int prow(int r) { return (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1); }
-PCS_DEV bf16x8 tr_frag2(const char *p0, const char *p1) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4 *)p1);
-  const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, v);
-}
+// x rows permuted (prow: bits 2 <-> 3) and padded
 
 // S1: also the column sums of dz5 (pcs_wgrad_args.dy_colsum; the opt-in four-wave global_feat
 // kernel's bn5 S1), a separate instantiation so that the default one keeps its registers
