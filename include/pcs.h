@@ -53,8 +53,7 @@ enum {
   PCS_PRO_RAW = 0,      /* a = A                                                        */
   PCS_PRO_BNRELU = 1,   /* a = max(A*s[k] + t[k], 0) [* keep(m,k) * keep_scale]  P:106-127 */
   PCS_PRO_BWD = 2,      /* a = alpha[k]*dZ[m,k] + beta[k] + gamma[k]*Y[m,k]   BN backward */
-  PCS_PRO_BWD_POOL = 3, /* a = beta[k] + gamma[k]*Y[m,k] + (m==am[b,k] ? sp[b,k] : 0)
-                           BN backward of bn_global fed by the max-pool (P:113-114)      */
+  /* 3: unused since ABI 3 (was PCS_PRO_BWD_POOL, the unfolded bn_global + max-pool backward) */
   PCS_PRO_CAT = 4       /* a = [A | relu(A2*s + t)] concatenated along k: columns k < K1 raw
                            from A [M, K1], columns K1.. from A2 [M, K-K1] through BN+ReLU
                            (s = pa, t = pb over A2's channels); W [Ncols, K1] for the first
@@ -92,15 +91,15 @@ typedef struct {
   int32_t prologue;     /* PCS_PRO_* */
   int32_t epilogue;     /* PCS_EPI_* */
   int32_t chunks_per_scene; /* 0 = auto; pcs_gemm_geometry() reports the value used */
-  const void *A;        /* [M,K] dtype: Y_{l-1} (fwd) | dZ_l (PRO_BWD) | Y_l (PRO_BWD_POOL) */
+  const void *A;        /* [M,K] dtype: Y_{l-1} (fwd) | dZ_l (PRO_BWD) */
   const void *A2;       /* [M,K] dtype: Y_l (PRO_BWD) */
   const float *pa;      /* [K] s (BNRELU) | alpha (BWD) */
-  const float *pb;      /* [K] t (BNRELU) | beta (BWD, BWD_POOL) */
-  const float *pc;      /* [K] gamma (BWD, BWD_POOL) */
+  const float *pb;      /* [K] t (BNRELU) | beta (BWD) */
+  const float *pc;      /* [K] gamma (BWD) */
   const uint8_t *a_mask;/* [M, K/8] dropout keep bits (BNRELU) or NULL */
   float a_keep_scale;   /* 1/(1-p) */
-  const int32_t *pool_idx; /* [B,K] argmax row (global index) (BWD_POOL) */
-  const float *pool_coef;  /* [B,K] alpha*dz at the argmax row (BWD_POOL) */
+  const int32_t *pool_idx; /* [B, pool_c] argmax row (global index) of the sparse rows (pool_w) */
+  const float *pool_coef;  /* [B, pool_c] their coefficient: alpha*dz at the argmax row (pool_w) */
   const void *W;        /* [Ncols, K] dtype */
   void *C;              /* [M, Ncols] dtype output */
   const float *bias;    /* [Ncols] (FWD) or NULL */
@@ -145,20 +144,20 @@ int pcs_conv1_fwd(const pcs_gemm_args *args, pcs_stream_t stream);
 
 /*
  * Weight gradient  dW[n, k] = sum_m dy[m, n] * x[m, k]   (autograd of P:106-128, P:254)
- * dy = pro_dy(dZ, Y) (PCS_PRO_BWD or PCS_PRO_BWD_POOL), x = pro_x(X) (PCS_PRO_BNRELU or
- * PCS_PRO_RAW).  The reduction over M is split into scene-aligned slices whose fp32
- * partials are summed in a fixed order (deterministic).
+ * dy = alpha*dZ + beta + gamma*Y (PCS_PRO_BWD) or dZ as stored (PCS_PRO_RAW), x = pro_x(X)
+ * (PCS_PRO_BNRELU or PCS_PRO_RAW).  The reduction over M is split into scene-aligned slices
+ * whose fp32 partials are summed in a fixed order (deterministic).
  */
 typedef struct {
   int64_t num_scenes, scene_rows;
   int32_t Cout, Cin;    /* dW is [Cout, Cin] */
   int32_t dtype;
   int32_t splits_per_scene; /* 0 = auto */
-  int32_t dy_mode;      /* PCS_PRO_BWD | PCS_PRO_BWD_POOL */
+  int32_t dy_mode;      /* PCS_PRO_BWD | PCS_PRO_RAW (PCS_PRO_BNRELU: pcs_gram's own); others: PCS_EINVAL */
   const void *dZ;       /* [M, Cout] */
   const void *Y;        /* [M, Cout] */
   const float *alpha, *beta, *gamma; /* [Cout] */
-  const int32_t *pool_idx; const float *pool_coef; /* [B, Cout] (BWD_POOL) */
+  const void *reserved0, *reserved1; /* see reserved2 */
   int32_t x_mode;       /* PCS_PRO_BNRELU | PCS_PRO_RAW */
   const void *X;        /* [M, Cin] dtype (f32 for conv1) */
   const float *s, *t;   /* [Cin] */
@@ -167,10 +166,9 @@ typedef struct {
   float *dW;            /* [Cout, Cin] f32 output, row stride ldw */
   int64_t ldw;          /* 0 = Cin */
   int32_t flags;        /* PCS_FLAG_GENERIC: never use the 256x256 wide-layer kernel */
-  float *dy_colsum;     /* [Cout] f32 or NULL: sum_m dy[m, n] (RAW dy, conv5's R pass only:
-                           bn5's S1 = the column sums of dz5 as stored, one ones-fragment MFMA
-                           per dz5 fragment beside R's; the workspace grows by one Cout row per
-                           slice).  Other kernels refuse it. */
+  void *reserved2;      /* reserved0..2 must be NULL (else PCS_EINVAL): they were pool_idx, pool_coef
+                           (BWD_POOL) and dy_colsum, removed in ABI 3; the kernels take this struct
+                           by value, so its layout stays */
 } pcs_wgrad_args;
 
 int64_t pcs_wgrad_workspace(pcs_wgrad_args *args); /* bytes; fills splits_per_scene */
@@ -179,26 +177,19 @@ int pcs_conv1_wgrad(const pcs_wgrad_args *args, pcs_stream_t stream); /* X = poi
                                                                           partial: B*splits*64*Cin f32 */
 
 /*
- * Fused input + weight gradient of seg_conv1's local half (bf16; Cout 512, Cin 64):
- * dy = alpha*dZ + beta + gamma*Y (dy_mode PCS_PRO_BWD), x = relu(X*s + t) (x_mode
- * PCS_PRO_BNRELU, no x_mask);  dX[M, 64] = dy . Wt^T (Wt = W^T, [64, 512] bf16, no epilogue)
- * and dW += dy^T x as pcs_wgrad (fp32 partials summed in a fixed order into dW, row stride
- * ldw).  Replaces the pcs_gemm(PRO_BWD, EPI_RAW) + pcs_wgrad pair, reading dy's inputs once.
- */
-int64_t pcs_dgrad_wgrad_workspace(pcs_wgrad_args *args); /* bytes; fills splits_per_scene */
-int pcs_dgrad_wgrad(const pcs_wgrad_args *args, const void *Wt, void *dX, pcs_stream_t stream);
-
-/*
- * The same two gradients in folded form, without reading bn_seg1's stored output Y'
- * (dy_mode PCS_PRO_RAW: dZ is bn_seg1's output gradient dz; x_mode PCS_PRO_BNRELU as above).
- * With dy = alpha dz + beta + gamma Y' and Y' = x W^T + scene_bias[b] (the stored seg_conv1
- * output, W = its local half as the forward GEMM saw it, fp32 [512, ldw]):
+ * Fused input + weight gradient of seg_conv1's local half (bf16; Cout 512, Cin 64), in folded
+ * form: without reading bn_seg1's stored output Y' (dy_mode PCS_PRO_RAW: dZ is bn_seg1's output
+ * gradient dz; x_mode PCS_PRO_BNRELU, no x_mask: x = relu(X*s + t)).  Replaces a pcs_gemm +
+ * pcs_wgrad pair.  With dy = alpha dz + beta + gamma Y' and Y' = x W^T + scene_bias[b] (the
+ * stored seg_conv1 output, W = its local half as the forward GEMM saw it, fp32 [512, ldw]):
  *   dX[m]  = dz[m] WaT^T + x[m] H + cvec[b],  cvec[b] = W^T (beta + gamma * scene_bias[b])
  *   dW     = diag(alpha) dz^T x + beta (x) S + diag(gamma) (W G + sum_b scene_bias[b] (x) S_b)
  * with WaT = (diag(alpha) W)^T [64, 512] and H = W^T diag(gamma) W [64, 64] in bf16 (pcs_bn_fold),
  * G = x^T x, S_b = per-scene column sums of x (collected by the same pass).  dW (fp32, columns
- * 0..63 of rows with stride ldw, as W) is written, not accumulated.  Workspace:
- * pcs_dgrad_wgrad_folded_workspace() bytes (partials, their sums and cvec).  One pass reads
+ * 0..63 of rows with stride ldw, as W) is written, not accumulated.  Workspace
+ * (pcs_dgrad_wgrad_folded_workspace() bytes), all fp32: one slab R [512, 64] | G [64, 64] | S [64]
+ * per slice (num_scenes * splits_per_scene slices), then the summed R | G, S_b [B, 64] and
+ * cvec [B, 64].  One pass reads
  * dz [M, 512] and X [M, 64] and writes dX: 1.2 KB per point instead of 2.3 KB.
  */
 int64_t pcs_dgrad_wgrad_folded_workspace(pcs_wgrad_args *args); /* bytes; fills splits_per_scene */
@@ -290,7 +281,8 @@ int pcs_scene_gemv(const float *g, int64_t num_scenes, int32_t Kg, const float *
  * from bn_seg1's backward coefficients builds csum[b,n] = sum_{rows of b} dy_seg1[:, n],
  * dW_seg1[:, 64:] = sum_b csum_b (x) g_b, dg = W_seg1[:, 64:]^T csum_b, dz_g = dg*(g>0),
  * then bn_global's (alpha, beta, gamma, dgamma, dbeta, dbias) and the sparse coefficient
- * sp[b,c] = alpha_c*dz_g[b,c] consumed by PCS_PRO_BWD_POOL.
+ * sp[b,c] = alpha_c*dz_g[b,c]: the pool_coef of pcs_gemm's pool_w rows and of pcs_pool_rows_add,
+ * and pcs_gram_wgrad's sp.
  */
 typedef struct {
   int64_t num_scenes, scene_rows;
@@ -819,9 +811,10 @@ int pcs_rows_segsum(const void *X, int32_t xdtype, const int32_t *src, const flo
 
 /* Build-time identification and error string. pcs_abi_version() returns PCS_ABI_VERSION,
  * bumped with every change to an argument struct's layout or an entry point's signature
- * (2: pcs_gemm_args gained `gram`, the w4 entry points were removed); a binding checks it
- * before its first call. */
-#define PCS_ABI_VERSION 2
+ * (2: pcs_gemm_args gained `gram`, the w4 entry points were removed; 3: prologue 3, three
+ * pcs_wgrad_args fields (now reserved) and the unfolded seg_conv1 entry points were removed); a
+ * binding checks it before its first call. */
+#define PCS_ABI_VERSION 3
 int pcs_abi_version(void);
 const char *pcs_last_error(void);
 

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libpcs.so")
 
 F32, BF16, FP8 = 0, 1, 2
-PRO_RAW, PRO_BNRELU, PRO_BWD, PRO_BWD_POOL, PRO_CAT = 0, 1, 2, 3, 4
+PRO_RAW, PRO_BNRELU, PRO_BWD, PRO_CAT = 0, 1, 2, 4
 EPI_FWD, EPI_DGRAD, EPI_RAW, EPI_BNRELU = 0, 1, 2, 3
 HEAD_FWD, HEAD_CE, HEAD_BWD = 0, 1, 2
 
@@ -55,10 +55,10 @@ class WgradArgs(ct.Structure):
         ("Cout", _i32), ("Cin", _i32), ("dtype", _i32), ("splits_per_scene", _i32),
         ("dy_mode", _i32),
         ("dZ", _vp), ("Y", _vp), ("alpha", _vp), ("beta", _vp), ("gamma", _vp),
-        ("pool_idx", _vp), ("pool_coef", _vp),
+        ("reserved0", _vp), ("reserved1", _vp),
         ("x_mode", _i32),
         ("X", _vp), ("s", _vp), ("t", _vp), ("x_mask", _vp), ("x_keep_scale", _f),
-        ("partial", _vp), ("dW", _vp), ("ldw", _i64), ("flags", _i32), ("dy_colsum", _vp),
+        ("partial", _vp), ("dW", _vp), ("ldw", _i64), ("flags", _i32), ("reserved2", _vp),
     ]
 
 
@@ -184,8 +184,6 @@ SIGNATURES = [
                                                  _vp]),
     ("pcs_confusion", ct.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp]),
     ("pcs_argmax", ct.c_int, [_vp, _i64, _i64, _i32, _vp, _vp]),
-    ("pcs_dgrad_wgrad_workspace", _i64, [ct.POINTER(WgradArgs)]),
-    ("pcs_dgrad_wgrad", ct.c_int, [ct.POINTER(WgradArgs), _vp, _vp, _vp]),
     ("pcs_dgrad_wgrad_bn_workspace", _i64, [ct.POINTER(GemmArgs)]),
     ("pcs_dgrad_wgrad_bn", ct.c_int, [ct.POINTER(GemmArgs), _vp, _vp, _i64, _vp]),
     ("pcs_round_weight", ct.c_int, [_vp, _i64, _i32, _vp, _vp]),
@@ -207,7 +205,7 @@ _lib = None
 
 
 # include/pcs.h PCS_ABI_VERSION: the layout of the structs mirrored in this file
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 
 class PcsError(RuntimeError):

@@ -1,22 +1,26 @@
-// Fused input + weight gradient of seg_conv1's local half (autograd of P:117-123 at P:254):
+// Fused input + weight gradient of seg_conv1's local half (autograd of P:117-123 at P:254), in
+// folded form: from bn_seg1's output gradient dz [M, 512] and x = relu(bn2(Y2)) [M, 64] alone,
+// without bn_seg1's stored output Y' = x W_l^T + scene_bias[b] (W_l = seg_conv1.weight[:, :64]).
+// With dy = alpha * dz + beta + gamma * Y' (the bn_seg1 backward):
 //
-//   dy      = alpha * dZ + beta + gamma * Y          (bn_seg1 backward, [M, 512])
-//   dA2     = dy . W_l                               ([M, 64], W_l = seg_conv1.weight[:, :64])
-//   dW_l   += dy^T . relu(bn2(Y2))                   ([512, 64])
+//   dA2[m]  = dy[m] . W_l   = dz[m] (diag(alpha) W_l) + x[m] H + cvec[b]          ([M, 64])
+//   dW_l    = dy^T . x      = diag(alpha) R + beta (x) S + diag(gamma) (W_l G + sum_b scene_bias[b] (x) S_b)
 //
-// Both gradients read the same dy, which is formed from the two widest tensors of the head
-// (dZ and Y of bn_seg1, 2 KB per point in bf16).  Separately (pcs_gemm + pcs_wgrad) they
-// read them twice; here each row slab is staged into LDS once and feeds both contractions,
-// so the pair moves 2.3 KB per point instead of 4.5 KB.  MFMA work is small (14 % of the
-// CU's MFMA time at the HBM rate), so the kernel is HBM-bound by design.
+// H = W_l^T diag(gamma) W_l and cvec[b] = W_l^T (beta + gamma * scene_bias[b]) (pcs_bn_fold
+// algebra), R = dz^T x, G = x^T x, S_b = per-scene column sums of x.  The kernel below makes one
+// pass over dz and x: it writes dA2 and per-slice partials of R, G and S; the kernels after it
+// sum the partials and assemble dW_l.  dz is the widest tensor of the head (1 KB per point in
+// bf16) and is staged into LDS once for both contractions.  MFMA work is small (14 % of the CU's
+// MFMA time at the HBM rate), so the kernel is HBM-bound by design.
 //
-// One 512-thread workgroup per CU (W_l^T stays resident in LDS for the workgroup's life),
-// scene-aligned row slices as pcs_wgrad, 64-row steps:
+// One 512-thread workgroup per CU ((diag(alpha) W_l)^T stays resident in LDS for the workgroup's
+// life), scene-aligned row slices as pcs_wgrad, 64-row steps:
 //   compute(step s) from LDS -> dA2 tile of step s to LDS -> barrier -> store it, write the
 //   registers (step s+1) into LDS, issue the loads of step s+2 -> barrier.
-// dgrad: wave w owns rows 16*(w>>1).. and columns 32*(w&1).. (2 accumulators, K = 512);
-// wgrad: wave w owns output channels 64*w.. x all 64 inputs (16 accumulators, K = 64 rows).
-// The dy tile is a [m][col] image (rows permuted as pcs_wgrad's bf16 tiles, 32-B padding)
+// dgrad: wave w owns rows 16*(w>>1).. and columns 32*(w&1).. (2 accumulators, K = 512 + 64);
+// wgrad: wave w owns output channels 64*w.. x all 64 inputs (16 accumulators, K = 64 rows) and
+// two 16-tiles of G.
+// The dz tile is a [m][col] image (rows permuted as pcs_wgrad's bf16 tiles, 32-B padding)
 // read with ds_read_b128 for the dgrad operand and ds_read_b64_tr_b16 for the wgrad one.
 #include "kernel_prims.h"
 
@@ -25,7 +29,7 @@ namespace {
 constexpr int THREADS = 512;
 constexpr int COUT = 512, CIN = 64, MS = 64;
 constexpr int WT_ROWB = COUT * 2;                  // W_l^T [CIN][COUT], XOR-swizzled 16-B slots
-constexpr int DY_ROWB = COUT * 2 + 32;             // dy [MS][COUT] (+32 B pad)
+constexpr int DY_ROWB = COUT * 2 + 32;             // dz [MS][COUT] (+32 B pad)
 constexpr int X_ROWB = CIN * 2 + 32;               // x  [MS][CIN]
 constexpr int OFF_DY = CIN * WT_ROWB;              // 64 KB
 constexpr int OFF_X = OFF_DY + MS * DY_ROWB;
@@ -33,15 +37,12 @@ constexpr int OFF_OUT = OFF_X + MS * X_ROWB;       // dA2 tile [MS][CIN] bf16, r
 // (+8 B: the epilogue's 8-B writes of 16 rows at one column hit 16 different banks -- 128-B rows
 // put them on two, 16-way (SQ_LDS_BANK_CONFLICT 0.38 of the LDS cycles, r06))
 constexpr int OUT_ROWB = CIN * 2 + 8;
-constexpr int OFF_COEF = OFF_OUT + MS * OUT_ROWB;  // alpha | beta | gamma [COUT], s | t [CIN]
-constexpr int LDS_BYTES = OFF_COEF + (3 * COUT + 2 * CIN) * 4;
-static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
-// folded form: s | t | cvec [CIN] f32, then H [CIN][CIN] bf16 (XOR-swizzled 16-B slots)
-constexpr int OFF_H = OFF_COEF + 3 * CIN * 4;
+constexpr int OFF_COEF = OFF_OUT + MS * OUT_ROWB;  // s | t | cvec [CIN] f32
+constexpr int OFF_H = OFF_COEF + 3 * CIN * 4;      // H [CIN][CIN] bf16 (XOR-swizzled 16-B slots)
 constexpr int H_ROWB = CIN * 2;
-constexpr int LDS_BYTES_F = OFF_H + CIN * H_ROWB;
-static_assert(LDS_BYTES_F <= 160 * 1024, "LDS budget (folded)");
-// folded form's per-slice partial slab: R = dz^T x [COUT][CIN] | G = x^T x [CIN][CIN] | S = sum x [CIN]
+constexpr int LDS_BYTES = OFF_H + CIN * H_ROWB;
+static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
+// per-slice partial slab: R = dz^T x [COUT][CIN] | G = x^T x [CIN][CIN] | S = sum x [CIN]
 constexpr int SLAB_F = COUT * CIN + CIN * CIN + CIN;
 constexpr int DY_CPR = COUT / 8, DY_RP = THREADS / DY_CPR, DY_NCH = MS / DY_RP;   // 64, 8, 8
 constexpr int X_CPR = CIN / 8, X_RP = THREADS / X_CPR;                            // 8, 64
@@ -55,18 +56,14 @@ PCS_DEV bf16x8 tr_read(const char *base, int r0, int r1, int rowb, int col) {
   return tr_frag2(base + r0 * rowb + col * 2, base + r1 * rowb + col * 2);
 }
 
-// FOLDED (dy_mode RAW): dy is dZ itself and Wt = (diag(alpha) W_l)^T, so the same contractions
-// give P = dZ (diag(alpha) W_l) and R = dZ^T x; the input gradient adds x H + cvec[scene] (H =
-// W_l^T diag(gamma) W_l, cvec = W_l^T (beta + gamma * scene_bias[b]), pcs_bn_fold algebra:
-// gamma * Y' W_l = x H + scene-bias terms, as Y' = x W_l^T + scene_bias[b]), and the slab also
-// collects G = x^T x and S = sum x for the Gram-form weight gradient (pcs_dgrad_wgrad_folded)
-// -- bn_seg1's stored Y' [M, 512] is not read at all.
-template <bool FOLDED>
+// a.dZ = dz, Wt = (diag(alpha) W_l)^T: the contractions give P = dz (diag(alpha) W_l) and
+// R = dz^T x; the input gradient adds x H + cvec[scene], and the slab also collects G = x^T x
+// and S = sum x for the Gram-form weight gradient (pcs_dgrad_wgrad_folded).
 __global__ __launch_bounds__(THREADS) void dgrad_wgrad_s1_kernel(pcs_wgrad_args a, const bf16_t *__restrict__ Wt,
                                                                  bf16_t *__restrict__ dX, int64_t rows_per_split,
                                                                  const bf16_t *__restrict__ Hg,
                                                                  const float *__restrict__ cvec) {
-  __shared__ __attribute__((aligned(16))) char lds[FOLDED ? LDS_BYTES_F : LDS_BYTES];
+  __shared__ __attribute__((aligned(16))) char lds[LDS_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int L = xcd_remap(blockIdx.x, gridDim.x);
   const int sps = a.splits_per_scene;
@@ -77,7 +74,6 @@ __global__ __launch_bounds__(THREADS) void dgrad_wgrad_s1_kernel(pcs_wgrad_args 
   const int64_t sbase = (int64_t)scene * N;
 
   const bf16_t *__restrict__ dZ = reinterpret_cast<const bf16_t *>(a.dZ);
-  const bf16_t *__restrict__ Yg = reinterpret_cast<const bf16_t *>(a.Y);
   const bf16_t *__restrict__ Xg = reinterpret_cast<const bf16_t *>(a.X);
 
   // W_l^T [CIN][COUT] -> LDS once (64 KB: 8 chunks per thread)
@@ -89,76 +85,48 @@ __global__ __launch_bounds__(THREADS) void dgrad_wgrad_s1_kernel(pcs_wgrad_args 
 
   // per-channel prologue coefficients -> LDS (read back at each store: fewer live registers)
   float *cf = reinterpret_cast<float *>(lds + OFF_COEF);
-  constexpr int CS = FOLDED ? 0 : 3 * COUT;   // x's bn2 scale | shift
-  if constexpr (FOLDED) {
-    if (tid < CIN) { cf[tid] = a.s[tid]; cf[CIN + tid] = a.t[tid]; cf[2 * CIN + tid] = cvec[scene * CIN + tid]; }
-    for (int i = tid; i < CIN * CIN / 8; i += THREADS) {   // H rows [c][j]
-      const int c = i / (CIN / 8), slot = i % (CIN / 8);
-      *reinterpret_cast<u32x4 *>(lds + OFF_H + c * H_ROWB + ((slot ^ (c & 7)) << 4)) =
-          *reinterpret_cast<const u32x4 *>(Hg + (int64_t)c * CIN + slot * 8);
-    }
-  } else {
-    for (int i = tid; i < COUT; i += THREADS) {
-      cf[i] = a.alpha[i]; cf[COUT + i] = a.beta[i]; cf[2 * COUT + i] = a.gamma[i];
-    }
-    if (tid < CIN) { cf[3 * COUT + tid] = a.s[tid]; cf[3 * COUT + CIN + tid] = a.t[tid]; }
+  if (tid < CIN) { cf[tid] = a.s[tid]; cf[CIN + tid] = a.t[tid]; cf[2 * CIN + tid] = cvec[scene * CIN + tid]; }
+  for (int i = tid; i < CIN * CIN / 8; i += THREADS) {   // H rows [c][j]
+    const int c = i / (CIN / 8), slot = i % (CIN / 8);
+    *reinterpret_cast<u32x4 *>(lds + OFF_H + c * H_ROWB + ((slot ^ (c & 7)) << 4)) =
+        *reinterpret_cast<const u32x4 *>(Hg + (int64_t)c * CIN + slot * 8);
   }
   __syncthreads();
 
-  // staging ownership: dy column chunk dc (8 channels), rows dr0 + 8 i; x chunk xc, row xr
+  // staging ownership: dz column chunk dc (8 channels), rows dr0 + 8 i; x chunk xc, row xr
   const int dc = tid % DY_CPR, dr0 = tid / DY_CPR;
   const int xc = tid % X_CPR, xr = tid / X_CPR;
 
-  u32x4 rz[DY_NCH], ry[DY_NCH], rx;
+  u32x4 rz[DY_NCH], rx;
   auto load_step = [&](int64_t m0) {   // rows clamped to the slice (zeroed at store time)
 #pragma unroll
     for (int i = 0; i < DY_NCH; ++i) {
       const int64_t r = pcs_min64(m0 + dr0 + DY_RP * i, hi - 1);
       const int64_t off = (sbase + r) * COUT + dc * 8;
       rz[i] = *reinterpret_cast<const u32x4 *>(dZ + off);
-      if constexpr (!FOLDED) ry[i] = *reinterpret_cast<const u32x4 *>(Yg + off);
     }
     const int64_t r = pcs_min64(m0 + xr, hi - 1);
     rx = *reinterpret_cast<const u32x4 *>(Xg + (sbase + r) * CIN + xc * 8);
   };
-  float xsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // FOLDED: this thread's column sums of x
+  float xsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // this thread's column sums of x
   auto store_step = [&](int64_t m0) {
-    if constexpr (FOLDED) {   // dy = dZ: a copy
 #pragma unroll
-      for (int i = 0; i < DY_NCH; ++i) {
-        const int rl = dr0 + DY_RP * i;
-        const u32x4 out = m0 + rl >= hi ? mk_u32x4(0, 0, 0, 0) : rz[i];
-        *reinterpret_cast<u32x4 *>(lds + OFF_DY + prow(rl) * DY_ROWB + dc * 16) = out;
-      }
-    } else {
-      float ca[8], cb[8], cg[8];
-      lds_vec8(cf + dc * 8, ca); lds_vec8(cf + COUT + dc * 8, cb); lds_vec8(cf + 2 * COUT + dc * 8, cg);
-#pragma unroll
-      for (int i = 0; i < DY_NCH; ++i) {
-        const int rl = dr0 + DY_RP * i;
-        float v[8], y[8];
-        unpack_chunk(rz[i], v);
-        unpack_chunk(ry[i], y);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaf(ca[e], v[e], fmaf(cg[e], y[e], cb[e]));
-        u32x4 out = pack_chunk(v);
-        if (m0 + rl >= hi) out = mk_u32x4(0, 0, 0, 0);
-        *reinterpret_cast<u32x4 *>(lds + OFF_DY + prow(rl) * DY_ROWB + dc * 16) = out;
-      }
+    for (int i = 0; i < DY_NCH; ++i) {   // dz: a copy
+      const int rl = dr0 + DY_RP * i;
+      const u32x4 out = m0 + rl >= hi ? mk_u32x4(0, 0, 0, 0) : rz[i];
+      *reinterpret_cast<u32x4 *>(lds + OFF_DY + prow(rl) * DY_ROWB + dc * 16) = out;
     }
     float v[8], xs[8], xt[8];
-    lds_vec8(cf + CS + xc * 8, xs); lds_vec8(cf + CS + CIN + xc * 8, xt);
+    lds_vec8(cf + xc * 8, xs); lds_vec8(cf + CIN + xc * 8, xt);
     unpack_chunk(rx, v);
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = relu(fmaf(v[e], xs[e], xt[e]));
     u32x4 out = pack_chunk(v);
     if (m0 + xr >= hi) out = mk_u32x4(0, 0, 0, 0);
-    if constexpr (FOLDED) {   // the sums of the stored (bf16) x, as the contractions see it
-      float d[8];
-      unpack_chunk(out, d);
+    float d[8];   // the sums of the stored (bf16) x, as the contractions see it
+    unpack_chunk(out, d);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) xsum[e] += d[e];
-    }
+    for (int e = 0; e < 8; ++e) xsum[e] += d[e];
     *reinterpret_cast<u32x4 *>(lds + OFF_X + prow(xr) * X_ROWB + xc * 16) = out;
   };
 
@@ -167,7 +135,7 @@ __global__ __launch_bounds__(THREADS) void dgrad_wgrad_s1_kernel(pcs_wgrad_args 
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) accw[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // FOLDED: G = x^T x, tiles (w / 2, 2 (w % 2) + u) of the 4 x 4 16-tiles
+  // G = x^T x, tiles (w / 2, 2 (w % 2) + u) of the 4 x 4 16-tiles
   f32x4 accg[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 
   const int nsteps = (int)((hi - lo + MS - 1) / MS);
@@ -184,12 +152,10 @@ __global__ __launch_bounds__(THREADS) void dgrad_wgrad_s1_kernel(pcs_wgrad_args 
   const char *tDY = lds + OFF_DY, *tX = lds + OFF_X;
   for (int st = 0; st < nsteps; ++st) {
     const int64_t m0 = lo + (int64_t)st * MS;
-    // dgrad: out^T[c][m] = sum_k Wt[c][k] dy[m][k]  (FOLDED: starts at cvec[c], + x H below)
-    f32x4 accd[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-    if constexpr (FOLDED) {
+    // dgrad: out^T[c][m] = cvec[c] + sum_k Wt[c][k] dz[m][k]  (+ x H below)
+    f32x4 accd[2];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) accd[j] = *reinterpret_cast<const f32x4 *>(cf + 2 * CIN + (cb0 + j) * 16 + 4 * g);
-    }
+    for (int j = 0; j < 2; ++j) accd[j] = *reinterpret_cast<const f32x4 *>(cf + 2 * CIN + (cb0 + j) * 16 + 4 * g);
     const int mrow = prow(mb * 16 + l16);
 #pragma unroll 4
     for (int kk = 0; kk < COUT / 32; ++kk) {
@@ -201,20 +167,18 @@ __global__ __launch_bounds__(THREADS) void dgrad_wgrad_s1_kernel(pcs_wgrad_args 
         accd[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, yf, accd[j], 0, 0, 0);
       }
     }
-    if constexpr (FOLDED) {   // + x H (K = 64: two k-steps over the staged x tile)
 #pragma unroll
-      for (int kk = 0; kk < CIN / 32; ++kk) {
-        const int slot = 4 * kk + g;
-        const bf16x8 xf = *reinterpret_cast<const bf16x8 *>(tX + mrow * X_ROWB + slot * 16);
+    for (int kk = 0; kk < CIN / 32; ++kk) {   // + x H (K = 64: two k-steps over the staged x tile)
+      const int slot = 4 * kk + g;
+      const bf16x8 xf = *reinterpret_cast<const bf16x8 *>(tX + mrow * X_ROWB + slot * 16);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int c = (cb0 + j) * 16 + l16;
-          const bf16x8 hf = *reinterpret_cast<const bf16x8 *>(lds + OFF_H + c * H_ROWB + ((slot ^ (c & 7)) << 4));
-          accd[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hf, xf, accd[j], 0, 0, 0);
-        }
+      for (int j = 0; j < 2; ++j) {
+        const int c = (cb0 + j) * 16 + l16;
+        const bf16x8 hf = *reinterpret_cast<const bf16x8 *>(lds + OFF_H + c * H_ROWB + ((slot ^ (c & 7)) << 4));
+        accd[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hf, xf, accd[j], 0, 0, 0);
       }
     }
-    // wgrad: dW[o][c] += sum_m dy[m][o] x[m][c]; lane group g holds m = 8g..8g+7 of 32
+    // wgrad: R[o][c] += sum_m dz[m][o] x[m][c]; lane group g holds m = 8g..8g+7 of 32
 #pragma unroll
     for (int kk = 0; kk < MS / 32; ++kk) {
       const int q = (lane >> 2) & 3, p = lane & 3;
@@ -229,13 +193,12 @@ __global__ __launch_bounds__(THREADS) void dgrad_wgrad_s1_kernel(pcs_wgrad_args 
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           accw[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[j], yf[i], accw[i][j], 0, 0, 0);
-      if constexpr (FOLDED) {   // fragments re-read at this wave's columns (no runtime register index)
-        const bf16x8 xi = tr_read(tX, r0, r1, X_ROWB, (wid >> 1) * 16 + 4 * p);
+      // G: fragments re-read at this wave's columns (no runtime register index)
+      const bf16x8 xi = tr_read(tX, r0, r1, X_ROWB, (wid >> 1) * 16 + 4 * p);
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const bf16x8 xj = tr_read(tX, r0, r1, X_ROWB, (2 * (wid & 1) + u) * 16 + 4 * p);
-          accg[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xj, xi, accg[u], 0, 0, 0);
-        }
+      for (int u = 0; u < 2; ++u) {
+        const bf16x8 xj = tr_read(tX, r0, r1, X_ROWB, (2 * (wid & 1) + u) * 16 + 4 * p);
+        accg[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xj, xi, accg[u], 0, 0, 0);
       }
     }
     // dA2 tile -> LDS: lane holds out[m = 16 mb + l16][c = 16 cb + 4 g + r]
@@ -260,25 +223,23 @@ __global__ __launch_bounds__(THREADS) void dgrad_wgrad_s1_kernel(pcs_wgrad_args 
     lds_barrier();
   }
 
-  // this slice's dW partial: lane holds dW[o = 64 w + 16 i + l16][c = 16 j + 4 g ..]
-  float *out = a.partial + (int64_t)L * (FOLDED ? SLAB_F : COUT * CIN);
-  if constexpr (FOLDED) {
-    // G tile (w / 2, 2 (w % 2) + u): lane holds G[16 (w / 2) + l16][16 (2 (w % 2) + u) + 4 g + r]
+  // this slice's slab: R, lane holds R[o = 64 w + 16 i + l16][c = 16 j + 4 g ..], written last
+  float *out = a.partial + (int64_t)L * SLAB_F;
+  // G tile (w / 2, 2 (w % 2) + u): lane holds G[16 (w / 2) + l16][16 (2 (w % 2) + u) + 4 g + r]
 #pragma unroll
-    for (int u = 0; u < 2; ++u)
-      *reinterpret_cast<float4 *>(out + COUT * CIN + ((wid >> 1) * 16 + l16) * CIN + (2 * (wid & 1) + u) * 16 + 4 * g) =
-          make_float4(accg[u][0], accg[u][1], accg[u][2], accg[u][3]);
-    // S: the 64 row-threads of each 8-column chunk, summed in a fixed order through LDS
-    __syncthreads();
-    float *red = reinterpret_cast<float *>(lds + OFF_DY);   // [64 rows][64 cols]
+  for (int u = 0; u < 2; ++u)
+    *reinterpret_cast<float4 *>(out + COUT * CIN + ((wid >> 1) * 16 + l16) * CIN + (2 * (wid & 1) + u) * 16 + 4 * g) =
+        make_float4(accg[u][0], accg[u][1], accg[u][2], accg[u][3]);
+  // S: the 64 row-threads of each 8-column chunk, summed in a fixed order through LDS
+  __syncthreads();
+  float *red = reinterpret_cast<float *>(lds + OFF_DY);   // [64 rows][64 cols]
 #pragma unroll
-    for (int e = 0; e < 8; ++e) red[xr * CIN + xc * 8 + e] = xsum[e];
-    __syncthreads();
-    if (tid < CIN) {
-      float t = 0.f;
-      for (int r = 0; r < X_RP; ++r) t += red[r * CIN + tid];
-      out[COUT * CIN + CIN * CIN + tid] = t;
-    }
+  for (int e = 0; e < 8; ++e) red[xr * CIN + xc * 8 + e] = xsum[e];
+  __syncthreads();
+  if (tid < CIN) {
+    float t = 0.f;
+    for (int r = 0; r < X_RP; ++r) t += red[r * CIN + tid];
+    out[COUT * CIN + CIN * CIN + tid] = t;
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -297,40 +258,10 @@ int64_t splits_of(const pcs_wgrad_args &a) {
   return sps < 1 ? 1 : sps;
 }
 
-bool shapes_ok(const pcs_wgrad_args &a) {
-  return a.dtype == PCS_BF16 && a.Cout == COUT && a.Cin == CIN && a.dy_mode == PCS_PRO_BWD &&
-         a.x_mode == PCS_PRO_BNRELU && !a.x_mask && !(a.flags & PCS_FLAG_GENERIC);
-}
-
 }  // namespace
 
-extern "C" int64_t pcs_dgrad_wgrad_workspace(pcs_wgrad_args *a) {
-  if (!a || a->num_scenes <= 0 || a->scene_rows <= 0) return pcs_set_einval("pcs_dgrad_wgrad_workspace", "bad geometry");
-  if (!shapes_ok(*a))
-    return pcs_set_einval("pcs_dgrad_wgrad_workspace",
-                          "bf16, Cout=512, Cin=64, dy_mode PRO_BWD, x_mode PRO_BNRELU, no x_mask only");
-  a->splits_per_scene = (int32_t)splits_of(*a);
-  return (int64_t)a->num_scenes * a->splits_per_scene * COUT * CIN * 4;
-}
-
-extern "C" int pcs_dgrad_wgrad(const pcs_wgrad_args *ap, const void *Wt, void *dX, pcs_stream_t stream) {
-  if (!ap || !Wt || !dX) return pcs_set_einval("pcs_dgrad_wgrad", "null argument");
-  pcs_wgrad_args a = *ap;
-  if (pcs_dgrad_wgrad_workspace(&a) < 0) return PCS_EINVAL;
-  if (!a.dZ || !a.Y || !a.alpha || !a.beta || !a.gamma || !a.X || !a.s || !a.t || !a.partial || !a.dW)
-    return pcs_set_einval("pcs_dgrad_wgrad", "missing operand");
-  if (a.scene_rows * a.num_scenes >= (int64_t)1 << 31) return pcs_set_einval("pcs_dgrad_wgrad", "M must be < 2^31");
-  const int64_t rps = ((a.scene_rows + a.splits_per_scene - 1) / a.splits_per_scene + MS - 1) / MS * MS;
-  const int nb = (int)(a.num_scenes * a.splits_per_scene);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(dgrad_wgrad_s1_kernel<false>, dim3(nb), dim3(THREADS), 0, s, a, static_cast<const bf16_t *>(Wt),
-                     static_cast<bf16_t *>(dX), rps, nullptr, nullptr);
-  PCS_CHECK_LAUNCH();
-  return pcs_reduce_partials(a.partial, nb, (int64_t)COUT * CIN, 1.0f, a.dW, a.ldw ? a.ldw : CIN, CIN, stream);
-}
-
 // ---------------------------------------------------------------------------------------
-// Folded form (pcs_dgrad_wgrad_folded): the slab sums, then the Gram-form weight gradient
+// After the pass (pcs_dgrad_wgrad_folded): the slab sums, then the Gram-form weight gradient
 //   dW_l = diag(alpha) R + beta (x) S + diag(gamma) (W_l G + sum_b scene_bias[b] (x) S_b)
 // (dy = alpha dz + beta + gamma Y', Y' = x W_l^T + scene_bias[b]), and the per-scene
 // constant row of the input gradient cvec[b] = W_l^T (beta + gamma * scene_bias[b]).
@@ -425,7 +356,7 @@ extern "C" int pcs_dgrad_wgrad_folded(const pcs_wgrad_args *ap, const void *WaT,
   float *cvec = Sb + B * CIN;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(folded_cvec_kernel, dim3(B), dim3(CIN), 0, s, W, a.ldw, a.beta, a.gamma, scene_bias, cvec);
-  hipLaunchKernelGGL(dgrad_wgrad_s1_kernel<true>, dim3(nb), dim3(THREADS), 0, s, a, static_cast<const bf16_t *>(WaT),
+  hipLaunchKernelGGL(dgrad_wgrad_s1_kernel, dim3(nb), dim3(THREADS), 0, s, a, static_cast<const bf16_t *>(WaT),
                      static_cast<bf16_t *>(dX), rps, static_cast<const bf16_t *>(H), cvec);
   hipLaunchKernelGGL(folded_reduce_kernel, dim3((RG_LEN + B * CIN + 255) / 256), dim3(256), 0, s, a.partial, nb,
                      a.splits_per_scene, B, red, Sb);

@@ -36,13 +36,12 @@ constexpr int RPP = THREADS / CPR;           // 16 rows per pass
 constexpr int NPASS = BM / RPP;              // 16 rows per thread in phase 2
 constexpr int LDS_MAIN = (2 * STAGE > CTILE) ? 2 * STAGE : CTILE;
 
-// LDS layout after the main area: prologue coefficients | argmax bitmap | epilogue
-// coefficients (DGRAD) | running per-column accumulators
+// LDS layout after the main area: prologue coefficients | epilogue coefficients (DGRAD) |
+// running per-column accumulators
 template <int PRO, int EPI> struct Lay {
-  static constexpr int NC = PRO == PCS_PRO_BNRELU ? 2 : PRO == PCS_PRO_BWD ? 3 : PRO == PCS_PRO_BWD_POOL ? 4 : 0;
+  static constexpr int NC = PRO == PCS_PRO_BNRELU ? 2 : PRO == PCS_PRO_BWD ? 3 : 0;
   static constexpr int COEF = LDS_MAIN;
-  static constexpr int BITS = COEF + NC * KMAX * 4;
-  static constexpr int ECOEF = BITS + (PRO == PCS_PRO_BWD_POOL ? 32 : 0);
+  static constexpr int ECOEF = COEF + NC * KMAX * 4;
   static constexpr int RUN = ECOEF + (EPI == PCS_EPI_DGRAD ? 4 * BN * 4 : 0);
   static constexpr int BYTES = RUN + (EPI == PCS_EPI_FWD ? 6 * BN * 4 : (EPI == PCS_EPI_DGRAD || EPI == PCS_EPI_BNRELU) ? 2 * BN * 4 : 0);
   static_assert(BYTES <= 160 * 1024, "LDS budget");
@@ -69,7 +68,6 @@ __global__ __launch_bounds__(THREADS) void gemm_big_kernel(pcs_gemm_args a, int 
   typedef Lay<PRO, EPI> LY;
   __shared__ __attribute__((aligned(16))) char lds[LY::BYTES];
   float *cf = reinterpret_cast<float *>(lds + LY::COEF);
-  uint32_t *tbits = reinterpret_cast<uint32_t *>(lds + LY::BITS);
   float *ecf = reinterpret_cast<float *>(lds + LY::ECOEF);   // DGRAD: es | et | emean | erstd
   float *run = reinterpret_cast<float *>(lds + LY::RUN);     // mean|m2|max|maxi|min|mini, S1|S2 or colsum
 
@@ -92,16 +90,12 @@ __global__ __launch_bounds__(THREADS) void gemm_big_kernel(pcs_gemm_args a, int 
   const bf16_t *__restrict__ Wg = reinterpret_cast<const bf16_t *>(a.W);
   bf16_t *__restrict__ Cg = reinterpret_cast<bf16_t *>(a.C);
 
-  // per-channel prologue coefficients -> LDS: c0 | c1 | c2 | pool argmax rows
+  // per-channel prologue coefficients -> LDS: c0 | c1 | c2
   for (int k = tid; k < K; k += THREADS) {
     if constexpr (PRO == PCS_PRO_BNRELU) {
       cf[k] = a.pa[k]; cf[KMAX + k] = a.pb[k];
     } else if constexpr (PRO == PCS_PRO_BWD) {
       cf[k] = a.pa[k]; cf[KMAX + k] = a.pb[k]; cf[2 * KMAX + k] = a.pc[k];
-    } else if constexpr (PRO == PCS_PRO_BWD_POOL) {
-      cf[k] = a.pool_coef[(int64_t)scene * K + k]; cf[KMAX + k] = a.pb[k];
-      cf[2 * KMAX + k] = a.pc[k];
-      reinterpret_cast<int *>(cf)[3 * KMAX + k] = a.pool_idx[(int64_t)scene * K + k];
     }
   }
   const bool do_stats = a.stats != nullptr, do_pool = EPI == PCS_EPI_FWD && a.pool != nullptr;
@@ -127,7 +121,6 @@ __global__ __launch_bounds__(THREADS) void gemm_big_kernel(pcs_gemm_args a, int 
 
   u32x4 ra[4], ra2[4], rb[4];
   uint32_t mk[4];
-  uint32_t hits = 0;   // POOL: bit i set if staging row srow + 64 i is an argmax row of the tile
   // Staging addresses: a uniform (SGPR) base per tile and k-step plus per-thread 32-bit byte
   // offsets computed once per tile (rows clamped to the tile's valid rows), so the loads use
   // the saddr + voffset form instead of 64-bit VALU address arithmetic every k-step.
@@ -161,8 +154,6 @@ __global__ __launch_bounds__(THREADS) void gemm_big_kernel(pcs_gemm_args a, int 
       lds_vec8(cf + k0, c0); lds_vec8(cf + KMAX + k0, c1);
     } else if constexpr (PRO == PCS_PRO_BWD) {
       lds_vec8(cf + k0, c0); lds_vec8(cf + KMAX + k0, c1); lds_vec8(cf + 2 * KMAX + k0, c2);
-    } else if constexpr (PRO == PCS_PRO_BWD_POOL) {
-      lds_vec8(cf + KMAX + k0, c1); lds_vec8(cf + 2 * KMAX + k0, c2);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -181,15 +172,6 @@ __global__ __launch_bounds__(THREADS) void gemm_big_kernel(pcs_gemm_args a, int 
         unpack_chunk(ra2[i], y);
 #pragma unroll
         for (int e = 0; e < EPC; ++e) v[e] = fmaf(c0[e], v[e], fmaf(c2[e], y[e], c1[e]));
-      } else if constexpr (PRO == PCS_PRO_BWD_POOL) {
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) v[e] = fmaf(c2[e], v[e], c1[e]);
-        if ((hits >> i) & 1u) {   // rare: this row is the max-pool argmax of some channel
-          const int grow = (int)(row_base + r);
-          const int *am = reinterpret_cast<const int *>(cf + 3 * KMAX);
-#pragma unroll
-          for (int e = 0; e < EPC; ++e) v[e] += am[k0 + e] == grow ? cf[k0 + e] : 0.f;
-        }
       }
       const u32x4 out = (PRO == PCS_PRO_RAW) ? ra[i] : pack_chunk(v);
       *reinterpret_cast<u32x4 *>(tA + r * ROWB + swz8(r, slot) * 16) = out;
@@ -220,22 +202,6 @@ __global__ __launch_bounds__(THREADS) void gemm_big_kernel(pcs_gemm_args a, int 
       for (int i = 0; i < 4; ++i) o[i] = nxt ? aoff_next[i] : aoff[i];
       load_stage(nxt ? next_base : row_base, o, tail ? 0 : ks_next);
     };
-    if constexpr (PRO == PCS_PRO_BWD_POOL) {   // bitmap of the tile's argmax rows
-      if (tid < BM / 32) tbits[tid] = 0u;
-      __syncthreads();
-      const int *am = reinterpret_cast<const int *>(cf + 3 * KMAX);
-      for (int c = tid; c < K; c += THREADS) {
-        const int64_t m = (int64_t)am[c] - row_base;
-        if (m >= 0 && m < valid) atomicOr(&tbits[m >> 5], 1u << (m & 31));
-      }
-      __syncthreads();
-      hits = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r = srow + 64 * i;
-        hits |= ((tbits[r >> 5] >> (r & 31)) & 1u) << i;
-      }
-    }
     store_stage(row_base, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     prefetch(1);
@@ -546,10 +512,8 @@ bool pcs_gemm_big_applicable(const pcs_gemm_args &a) {
   if (a.epilogue == PCS_EPI_FWD || a.epilogue == PCS_EPI_BNRELU)
     return a.prologue == PCS_PRO_BNRELU || a.prologue == PCS_PRO_RAW;
   if (a.epilogue == PCS_EPI_DGRAD && (!a.es || !a.erstd || a.bias || a.pool_w)) return false;
-  if (a.epilogue == PCS_EPI_DGRAD)   // BWD_POOL (global_feat) has neither a mask nor an addend
-    return a.prologue == PCS_PRO_BWD ? !(a.c_mask && a.addend)
-                                     : a.prologue == PCS_PRO_BWD_POOL && !a.c_mask && !a.addend;
-  if (a.epilogue == PCS_EPI_RAW) return a.prologue == PCS_PRO_BWD || a.prologue == PCS_PRO_BWD_POOL;
+  if (a.epilogue == PCS_EPI_DGRAD) return a.prologue == PCS_PRO_BWD && !(a.c_mask && a.addend);
+  if (a.epilogue == PCS_EPI_RAW) return a.prologue == PCS_PRO_BWD;
   return false;
 }
 
@@ -567,12 +531,10 @@ int pcs_gemm_big_launch(const pcs_gemm_args &g, int tps, int tpc, hipStream_t s)
       return g.a_mask ? launch<PCS_PRO_BNRELU, PCS_EPI_BNRELU, true>(g, tps, tpc, s)
                       : launch<PCS_PRO_BNRELU, PCS_EPI_BNRELU, false>(g, tps, tpc, s);
     case PCS_EPI_DGRAD:
-      if (g.prologue == PCS_PRO_BWD_POOL) return launch<PCS_PRO_BWD_POOL, PCS_EPI_DGRAD, false>(g, tps, tpc, s);
       if (g.c_mask) return launch<PCS_PRO_BWD, PCS_EPI_DGRAD, true>(g, tps, tpc, s);
       if (g.addend) return launch<PCS_PRO_BWD, PCS_EPI_DGRAD, false, true>(g, tps, tpc, s);
       return launch<PCS_PRO_BWD, PCS_EPI_DGRAD, false>(g, tps, tpc, s);
     default:
-      return g.prologue == PCS_PRO_BWD_POOL ? launch<PCS_PRO_BWD_POOL, PCS_EPI_RAW, false>(g, tps, tpc, s)
-                                            : launch<PCS_PRO_BWD, PCS_EPI_RAW, false>(g, tps, tpc, s);
+      return launch<PCS_PRO_BWD, PCS_EPI_RAW, false>(g, tps, tpc, s);
   }
 }

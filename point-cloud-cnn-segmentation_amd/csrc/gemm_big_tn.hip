@@ -3,10 +3,10 @@
 //
 // * 512 threads = 8 waves as 2 (Cout) x 4 (Cin); each wave owns 128 x 64 outputs
 //   (8 x 4 v_mfma_f32_16x16x32_bf16 accumulators), 64 MFMAs per 64-row step.
-// * dy = beta + gamma*y_g (+ alpha*dz at the max-pool argmax rows) and x = relu(bn5(y5))
-//   are formed while staging [64 rows x 256 cols] tiles global -> VGPR -> LDS; the MFMA
-//   operands are read back transposed with ds_read_b64_tr_b16 (rows permuted + 32-B
-//   padded: the 8 rows one transposed read touches hit 8 distinct bank groups).
+// * dy = alpha*dz + beta + gamma*y and x = relu(X*s + t) are formed while staging
+//   [64 rows x 256 cols] tiles global -> VGPR -> LDS; the MFMA operands are read back
+//   transposed with ds_read_b64_tr_b16 (rows permuted + 32-B padded: the 8 rows one
+//   transposed read touches hit 8 distinct bank groups).
 // * the M reduction is split into scene-aligned row slices; each workgroup writes one
 //   fp32 partial tile and pcs_reduce_partials sums them in a fixed order.
 // * Gram mode (DYMODE = PCS_PRO_BNRELU, pcs_gram): both operands are a = relu(Y*s + t) of
@@ -21,7 +21,9 @@ constexpr int TM = 256, TN = 256, MS = 64;
 constexpr int ROWB = TM * 2 + 32;          // 544 B: padded LDS row
 constexpr int OPB = MS * ROWB;             // one operand tile (34 KB)
 constexpr int STAGE = 2 * OPB;
-constexpr int COEF = 6 * 256 * 4;          // alpha|beta|gamma|argmax (Cout cols), s|t (Cin cols)
+// alpha|beta|gamma|unused (Cout cols), s|t (Cin cols).  The fourth slot held the max-pool argmax
+// until ABI 3; it stays because the LDS size and the s|t offsets are part of the kernels' code.
+constexpr int COEF = 6 * 256 * 4;
 constexpr int LDS_BYTES = 2 * STAGE + COEF;
 
 PCS_DEV bf16x8 tr_frag(const char *tile, int r0, int r1, int col) {
@@ -58,7 +60,7 @@ PCS_DEV void lds8(const float *p, float (&v)[8]) {
 }
 
 // Transform one staged 64-row step (dy and x) and write it to LDS.  Coefficients come from
-// the workgroup's LDS copy (cf: [alpha|pool coef][beta][gamma][argmax] over its 256 Cout
+// the workgroup's LDS copy (cf: [alpha][beta][gamma][unused] over its 256 Cout
 // columns, [s][t] over its 256 Cin columns); rows past the slice end are written as zeros.
 template <int DYMODE, bool MASK, bool RAWG = false>
 PCS_DEV void tn_store(const pcs_wgrad_args &a, char *tA, const float *cf, int64_t rbase, int64_t rlast,
@@ -87,16 +89,9 @@ PCS_DEV void tn_store(const pcs_wgrad_args &a, char *tA, const float *cf, int64_
   const int c8 = cc * 8;
   {
     float ca[8], cb[8], cg[8];
-    int am[8];
     lds8(cf + c8, ca);
     lds8(cf + 256 + c8, cb);
     lds8(cf + 512 + c8, cg);
-    if constexpr (DYMODE == PCS_PRO_BWD_POOL) {
-      const int4 i0 = *reinterpret_cast<const int4 *>(cf + 768 + c8);
-      const int4 i1 = *reinterpret_cast<const int4 *>(cf + 768 + c8 + 4);
-      am[0] = i0.x; am[1] = i0.y; am[2] = i0.z; am[3] = i0.w;
-      am[4] = i1.x; am[5] = i1.y; am[6] = i1.z; am[7] = i1.w;
-    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int rl = r0 + 16 * i;
@@ -107,16 +102,9 @@ PCS_DEV void tn_store(const pcs_wgrad_args &a, char *tA, const float *cf, int64_
         unpack_chunk(rz[i], v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = fmaf(ca[e], v[e], fmaf(cg[e], y[e], cb[e]));
-      } else if constexpr (DYMODE == PCS_PRO_BNRELU) {   // Gram: (beta, gamma) slots hold (s, t)
+      } else {   // Gram (PCS_PRO_BNRELU): (beta, gamma) slots hold (s, t)
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = relu(fmaf(y[e], cb[e], cg[e]));
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float x = fmaf(cg[e], y[e], cb[e]);
-          if (am[e] == (int)r) x += ca[e];
-          v[e] = x;
-        }
       }
       u32x4 o = pack_chunk(v);
       if (r >= rlast) o = mk_u32x4(0, 0, 0, 0);
@@ -181,12 +169,7 @@ __global__ __launch_bounds__(THREADS) void wgrad_big_kernel(pcs_wgrad_args a, in
   const int cc = tid & 31, r0 = tid >> 5;   // staging: fixed 8-column chunk, rows r0 + 16 i
   const int an = n0 + cc * 8, bk = k0 + cc * 8;
   for (int c = tid; c < 256; c += THREADS) {
-    if constexpr (DYMODE == PCS_PRO_BWD) {
-      cf[c] = a.alpha[n0 + c];
-    } else if constexpr (DYMODE == PCS_PRO_BWD_POOL) {
-      cf[c] = a.pool_coef[(int64_t)scene * Cout + n0 + c];
-      reinterpret_cast<int *>(cf)[768 + c] = a.pool_idx[(int64_t)scene * Cout + n0 + c];
-    }
+    if constexpr (DYMODE == PCS_PRO_BWD) cf[c] = a.alpha[n0 + c];
     if constexpr (RAWG) continue;
     if constexpr (DYMODE == PCS_PRO_BNRELU) {
       cf[256 + c] = a.s[n0 + c];
@@ -278,7 +261,7 @@ bool pcs_wgrad_big_applicable(const pcs_wgrad_args &a) {
   if (a.dy_mode == PCS_PRO_BNRELU && (a.Cout != a.Cin || a.x_mask)) return false;   // Gram: square
   return !(a.flags & PCS_FLAG_GENERIC) && a.dtype == PCS_BF16 && a.Cout % TM == 0 && a.Cin % TN == 0 &&
          a.x_mode == PCS_PRO_BNRELU &&
-         (a.dy_mode == PCS_PRO_BWD || a.dy_mode == PCS_PRO_BWD_POOL || a.dy_mode == PCS_PRO_BNRELU);
+         (a.dy_mode == PCS_PRO_BWD || a.dy_mode == PCS_PRO_BNRELU);
 }
 
 int pcs_wgrad_big_tiles(const pcs_wgrad_args &a) {
@@ -315,9 +298,6 @@ int pcs_wgrad_big_launch(const pcs_wgrad_args &a, hipStream_t s) {
                          ntiles);
     else
       hipLaunchKernelGGL((wgrad_big_kernel<PCS_PRO_BNRELU, false>), dim3(nb), dim3(THREADS), 0, s, a, rps, ntn, ntiles);
-  } else if (a.dy_mode == PCS_PRO_BWD_POOL) {
-    if (a.x_mask) hipLaunchKernelGGL((wgrad_big_kernel<PCS_PRO_BWD_POOL, true>), dim3(nb), dim3(THREADS), 0, s, a, rps, ntn, ntiles);
-    else hipLaunchKernelGGL((wgrad_big_kernel<PCS_PRO_BWD_POOL, false>), dim3(nb), dim3(THREADS), 0, s, a, rps, ntn, ntiles);
   } else {
     if (a.x_mask) hipLaunchKernelGGL((wgrad_big_kernel<PCS_PRO_BWD, true>), dim3(nb), dim3(THREADS), 0, s, a, rps, ntn, ntiles);
     else hipLaunchKernelGGL((wgrad_big_kernel<PCS_PRO_BWD, false>), dim3(nb), dim3(THREADS), 0, s, a, rps, ntn, ntiles);

@@ -54,8 +54,7 @@ template <> struct Mfma<float> {
 constexpr int KMAX = 1024;   // prologue coefficient arrays staged in LDS (K <= KMAX)
 
 template <int PRO> struct Coef {   // per-channel prologue arrays kept in LDS
-  static constexpr int N = (PRO == PCS_PRO_BNRELU || PRO == PCS_PRO_CAT) ? 2 : PRO == PCS_PRO_BWD ? 3
-                           : PRO == PCS_PRO_BWD_POOL ? 4 : 0;
+  static constexpr int N = (PRO == PCS_PRO_BNRELU || PRO == PCS_PRO_CAT) ? 2 : PRO == PCS_PRO_BWD ? 3 : 0;
 };
 
 template <int EPC>
@@ -110,10 +109,9 @@ PCS_DEV void nt_load(const pcs_gemm_args &a, const T *__restrict__ Ag, const T *
 
 // ... then prologue transform (coefficients from LDS) and registers -> LDS
 template <typename T, int BM, int BN, int PRO, bool MASK>
-PCS_DEV void nt_store(const pcs_gemm_args &a, char *tA, const float *cf, int64_t row_base, int valid,
-                      int k0, int slot, int srow, const u32x4 (&ra)[BM / 64],
-                      const u32x4 (&ra2)[BM / 64], const u32x4 (&rb)[BN / 64],
-                      const uint32_t (&mk)[BM / 64]) {
+PCS_DEV void nt_store(const pcs_gemm_args &a, char *tA, const float *cf, int valid, int k0, int slot,
+                      int srow, const u32x4 (&ra)[BM / 64], const u32x4 (&ra2)[BM / 64],
+                      const u32x4 (&rb)[BN / 64], const uint32_t (&mk)[BM / 64]) {
   constexpr int EPC = Elem<T>::EPC;
   char *tB = tA + BM * ROWB;
   float c0[EPC], c1[EPC], c2[EPC];
@@ -122,7 +120,7 @@ PCS_DEV void nt_store(const pcs_gemm_args &a, char *tA, const float *cf, int64_t
     lds_vec<EPC>(cf + k0, c0); lds_vec<EPC>(cf + KMAX + k0, c1);
   } else if constexpr (PRO == PCS_PRO_CAT) {
     if (cat2) { lds_vec<EPC>(cf + (k0 - a.K1), c0); lds_vec<EPC>(cf + KMAX + (k0 - a.K1), c1); }
-  } else if constexpr (PRO == PCS_PRO_BWD || PRO == PCS_PRO_BWD_POOL) {
+  } else if constexpr (PRO == PCS_PRO_BWD) {
     lds_vec<EPC>(cf + k0, c0); lds_vec<EPC>(cf + KMAX + k0, c1); lds_vec<EPC>(cf + 2 * KMAX + k0, c2);
   }
 #pragma unroll
@@ -147,11 +145,6 @@ PCS_DEV void nt_store(const pcs_gemm_args &a, char *tA, const float *cf, int64_t
       unpack_chunk(ra2[i], y);
 #pragma unroll
       for (int e = 0; e < EPC; ++e) v[e] = fmaf(c0[e], v[e], fmaf(c2[e], y[e], c1[e]));
-    } else if constexpr (PRO == PCS_PRO_BWD_POOL) {
-      const int grow = (int)(row_base + r);
-      const int *am = reinterpret_cast<const int *>(cf + 3 * KMAX) + k0;
-#pragma unroll
-      for (int e = 0; e < EPC; ++e) v[e] = fmaf(c2[e], v[e], c1[e]) + (am[e] == grow ? c0[e] : 0.f);
     }
     u32x4 out = (PRO == PCS_PRO_RAW || (PRO == PCS_PRO_CAT && !cat2)) ? ra[i] : pack_chunk(v);
     if (r >= valid) out = mk_u32x4(0, 0, 0, 0);
@@ -219,9 +212,6 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_nt_kernel(pcs_gemm_args a, in
       cf[k] = a.pa[k]; cf[KMAX + k] = a.pb[k];
     } else if constexpr (PRO == PCS_PRO_BWD) {
       cf[k] = a.pa[k]; cf[KMAX + k] = a.pb[k]; cf[2 * KMAX + k] = a.pc[k];
-    } else if constexpr (PRO == PCS_PRO_BWD_POOL) {
-      cf[k] = a.pool_coef[(int64_t)scene * K + k]; cf[KMAX + k] = a.pb[k]; cf[2 * KMAX + k] = a.pc[k];
-      reinterpret_cast<int *>(cf)[3 * KMAX + k] = a.pool_idx[(int64_t)scene * K + k];
     }
   }
   if constexpr (EPI == PCS_EPI_DGRAD) {   // NULL es/et: mask Yp > 0; NULL erstd: no S2
@@ -292,7 +282,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_nt_kernel(pcs_gemm_args a, in
 #pragma unroll
       for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    nt_store<T, BM, BN, PRO, MASK>(a, lds, cf, row_base, valid, slot * EPC, slot, srow, ra, ra2, rb, mk);
+    nt_store<T, BM, BN, PRO, MASK>(a, lds, cf, valid, slot * EPC, slot, srow, ra, ra2, rb, mk);
     __builtin_amdgcn_sched_barrier(0);
     prefetch(1);
     lds_barrier();
@@ -313,7 +303,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_nt_kernel(pcs_gemm_args a, in
           for (int j = 0; j < FN; ++j) acc[i][j] = Mfma<T>::mma(bf[j], af[i], acc[i][j]);
       }
       if (ks + 1 < nks) {
-        nt_store<T, BM, BN, PRO, MASK>(a, lds + (buf ^ 1) * (BM + BN) * ROWB, cf, row_base, valid,
+        nt_store<T, BM, BN, PRO, MASK>(a, lds + (buf ^ 1) * (BM + BN) * ROWB, cf, valid,
                                        (ks + 1) * KSTEP + slot * EPC, slot, srow, ra, ra2, rb, mk);
         __builtin_amdgcn_sched_barrier(0);
         prefetch(ks + 2);
@@ -535,8 +525,6 @@ int dispatch_pro_epi(const pcs_gemm_args &a, int tps, int tpc, hipStream_t s) {
     case PCS_EPI_DGRAD:
       switch (a.prologue) {
         case PCS_PRO_BWD: return launch_t<T, BM, BN, PCS_PRO_BWD, PCS_EPI_DGRAD, false>(a, tps, tpc, s);
-        case PCS_PRO_BWD_POOL:
-          return launch_t<T, BM, BN, PCS_PRO_BWD_POOL, PCS_EPI_DGRAD, false>(a, tps, tpc, s);
         case PCS_PRO_BNRELU:   // a_{l-1} H (folded BN backward of a wide layer, see pcs_bn_fold)
           return launch_t<T, BM, BN, PCS_PRO_BNRELU, PCS_EPI_DGRAD, false>(a, tps, tpc, s);
         case PCS_PRO_CAT:      // dz5 (diag alpha W5) + a4 H4 + c (conv5, folded, one pass)
@@ -557,8 +545,6 @@ int dispatch_pro_epi(const pcs_gemm_args &a, int tps, int tpc, hipStream_t s) {
     case PCS_EPI_RAW:
       switch (a.prologue) {
         case PCS_PRO_BWD: return launch_t<T, BM, BN, PCS_PRO_BWD, PCS_EPI_RAW, false>(a, tps, tpc, s);
-        case PCS_PRO_BWD_POOL:
-          return launch_t<T, BM, BN, PCS_PRO_BWD_POOL, PCS_EPI_RAW, false>(a, tps, tpc, s);
         case PCS_PRO_BNRELU:
           return launch_t<T, BM, BN, PCS_PRO_BNRELU, PCS_EPI_RAW, false>(a, tps, tpc, s);
         default: break;
@@ -603,6 +589,9 @@ extern "C" int64_t pcs_gemm_geometry(pcs_gemm_args *a) {
 extern "C" int pcs_gemm(const pcs_gemm_args *ap, pcs_stream_t stream) {
   if (!ap) return pcs_set_einval("pcs_gemm", "null args");
   pcs_gemm_args a = *ap;
+  if (a.prologue != PCS_PRO_RAW && a.prologue != PCS_PRO_BNRELU && a.prologue != PCS_PRO_BWD &&
+      a.prologue != PCS_PRO_CAT)
+    return pcs_set_einval("pcs_gemm", "unknown prologue (PCS_PRO_RAW, PCS_PRO_BNRELU, PCS_PRO_BWD or PCS_PRO_CAT)");
   if (a.K <= 0 || a.Ncols <= 0) return pcs_set_einval("pcs_gemm", "K/Ncols must be positive");
   if (a.Ncols % 64 != 0) return pcs_set_einval("pcs_gemm", "Ncols must be a multiple of 64");
   const int kstep = a.dtype == PCS_BF16 ? 32 : 16;
@@ -610,8 +599,6 @@ extern "C" int pcs_gemm(const pcs_gemm_args *ap, pcs_stream_t stream) {
   if (!a.A || !a.W) return pcs_set_einval("pcs_gemm", "A and W are required");
   if (a.prologue == PCS_PRO_BWD && (!a.A2 || !a.pa || !a.pb || !a.pc))
     return pcs_set_einval("pcs_gemm", "PRO_BWD needs A2 (=Y_l), alpha, beta, gamma");
-  if (a.prologue == PCS_PRO_BWD_POOL && (!a.pb || !a.pc || !a.pool_idx || !a.pool_coef))
-    return pcs_set_einval("pcs_gemm", "PRO_BWD_POOL needs beta, gamma, pool_idx, pool_coef");
   if (a.prologue == PCS_PRO_BNRELU && (!a.pa || !a.pb))
     return pcs_set_einval("pcs_gemm", "PRO_BNRELU needs s and t");
   if (a.epilogue < PCS_EPI_FWD || a.epilogue > PCS_EPI_BNRELU) return pcs_set_einval("pcs_gemm", "bad epilogue");

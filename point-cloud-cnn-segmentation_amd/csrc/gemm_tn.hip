@@ -3,7 +3,7 @@
 //   dW[n, k] = sum_m dy[m, n] * x[m, k]
 //
 // dy is formed on the fly from the stored BN-input Y_l and the ReLU-masked gradient dZ_l
-// (dy = alpha*dz + beta + gamma*y, or the max-pool sparse form for bn_global) and x from
+// (dy = alpha*dz + beta + gamma*y, or dz as stored) and x from
 // the previous layer's stored Y_{l-1} (relu(bn(y)) * dropout keep bits), so neither dy
 // nor x is ever materialised.  The M reduction is split into scene-aligned row slices,
 // each workgroup writes an fp32 partial tile, and pcs_reduce_partials sums the slices in
@@ -75,14 +75,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_kernel(pcs_wgrad_args a, int
   const int bcc = tid % OB::CPR, br0 = tid / OB::CPR;
   const int an = n0 + acc_c * EPC, bk = k0 + bcc * EPC;
   float ca[EPC], cb[EPC], cg[EPC], xs[EPC], xt[EPC];
-  int am[EPC];
-  if constexpr (DYMODE == PCS_PRO_BWD) {
-    load_vec<EPC>(a.alpha, an, ca);
-  } else if constexpr (DYMODE == PCS_PRO_BWD_POOL) {
-    load_vec<EPC>(a.pool_coef + scene * Cout, an, ca);
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) am[e] = a.pool_idx[scene * Cout + an + e];
-  }
+  if constexpr (DYMODE == PCS_PRO_BWD) load_vec<EPC>(a.alpha, an, ca);
   if constexpr (DYMODE == PCS_PRO_BNRELU) {   // Gram: dy = relu(y*s + t) of the same activations
     load_vec<EPC>(a.s, an, cb);
     load_vec<EPC>(a.t, an, cg);
@@ -136,13 +129,9 @@ __global__ __launch_bounds__(THREADS, 2) void wgrad_kernel(pcs_wgrad_args a, int
         unpack_chunk(rz[i], v);
 #pragma unroll
         for (int e = 0; e < EPC; ++e) v[e] = fmaf(ca[e], v[e], fmaf(cg[e], y[e], cb[e]));
-      } else if constexpr (DYMODE == PCS_PRO_BNRELU) {
+      } else {   // PCS_PRO_BNRELU
 #pragma unroll
         for (int e = 0; e < EPC; ++e) v[e] = relu(fmaf(y[e], cb[e], cg[e]));
-      } else {
-        const int grow = (int)(scene * N + r);
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) v[e] = fmaf(cg[e], y[e], cb[e]) + (am[e] == grow ? ca[e] : 0.f);
       }
       u32x4 out = pack_chunk(v);
       if (r >= hi) out = mk_u32x4(0, 0, 0, 0);
@@ -296,8 +285,6 @@ int dispatch_modes(const pcs_wgrad_args &a, int64_t rps, hipStream_t s) {
   if (a.dy_mode == PCS_PRO_BWD) {
     if (a.x_mode == PCS_PRO_BNRELU) return launch<T, TM, TN, PCS_PRO_BWD, PCS_PRO_BNRELU>(a, rps, s);
     if (a.x_mode == PCS_PRO_RAW) return launch<T, TM, TN, PCS_PRO_BWD, PCS_PRO_RAW>(a, rps, s);
-  } else if (a.dy_mode == PCS_PRO_BWD_POOL) {
-    if (a.x_mode == PCS_PRO_BNRELU) return launch<T, TM, TN, PCS_PRO_BWD_POOL, PCS_PRO_BNRELU>(a, rps, s);
   } else if (a.dy_mode == PCS_PRO_RAW) {
     if (a.x_mode == PCS_PRO_BNRELU) return launch<T, TM, TN, PCS_PRO_RAW, PCS_PRO_BNRELU>(a, rps, s);
   } else if (a.dy_mode == PCS_PRO_BNRELU && a.x_mode == PCS_PRO_BNRELU && !a.x_mask) {
@@ -320,11 +307,15 @@ int64_t rows_per_split_of(const pcs_wgrad_args &a, int ms) {
   return (rps + ms - 1) / ms * ms;
 }
 
+// a caller built against ABI 2 may still fill the three fields ABI 3 removed (pcs.h)
+bool reserved_set(const pcs_wgrad_args &a) { return a.reserved0 || a.reserved1 || a.reserved2; }
+
 }  // namespace
 
 extern "C" int64_t pcs_wgrad_workspace(pcs_wgrad_args *a) {
   if (!a || a->num_scenes <= 0 || a->scene_rows <= 0 || a->Cout <= 0 || a->Cin <= 0)
     return pcs_set_einval("pcs_wgrad_workspace", "bad geometry");
+  if (reserved_set(*a)) return pcs_set_einval("pcs_wgrad_workspace", "reserved0..2 must be NULL (removed in ABI 3)");
   const int ms = a->dtype == PCS_BF16 ? TnCfg<bf16_t>::MS : TnCfg<float>::MS;
   if (a->splits_per_scene <= 0 && pcs_wgrad_c5_class(*a)) a->splits_per_scene = pcs_wgrad_c5_splits(*a);
   if (a->splits_per_scene <= 0 && pcs_wgrad_big_applicable(*a)) a->splits_per_scene = pcs_wgrad_big_splits(*a);
@@ -339,22 +330,21 @@ extern "C" int64_t pcs_wgrad_workspace(pcs_wgrad_args *a) {
     a->splits_per_scene = (int32_t)sps;
   }
   const int64_t nslabs = (int64_t)a->num_scenes * a->splits_per_scene;
-  return nslabs * a->Cout * a->Cin * 4 + (a->dy_colsum ? nslabs * a->Cout * 4 : 0);
+  return nslabs * a->Cout * a->Cin * 4;
 }
 
 extern "C" int pcs_wgrad(const pcs_wgrad_args *ap, pcs_stream_t stream) {
   if (!ap) return pcs_set_einval("pcs_wgrad", "null args");
   pcs_wgrad_args a = *ap;
+  if (reserved_set(a)) return pcs_set_einval("pcs_wgrad", "reserved0..2 must be NULL (removed in ABI 3)");
+  if (a.dy_mode != PCS_PRO_RAW && a.dy_mode != PCS_PRO_BNRELU && a.dy_mode != PCS_PRO_BWD)
+    return pcs_set_einval("pcs_wgrad", "unknown dy_mode (PCS_PRO_RAW, PCS_PRO_BNRELU or PCS_PRO_BWD)");
   if (a.Cout % 64 || a.Cin % 64) return pcs_set_einval("pcs_wgrad", "Cout/Cin must be multiples of 64");
   if (!a.X || !a.partial || !a.dW) return pcs_set_einval("pcs_wgrad", "missing operand");
   if (a.dy_mode == PCS_PRO_RAW ? !a.dZ : (!a.Y || !a.beta || !a.gamma))
-    return pcs_set_einval("pcs_wgrad", "dy operands missing (RAW: dZ; BWD/BWD_POOL: Y, beta, gamma)");
+    return pcs_set_einval("pcs_wgrad", "dy operands missing (RAW: dZ; otherwise: Y, beta, gamma)");
   if (a.dy_mode == PCS_PRO_BWD && (!a.dZ || !a.alpha)) return pcs_set_einval("pcs_wgrad", "PRO_BWD needs dZ, alpha");
-  if (a.dy_mode == PCS_PRO_BWD_POOL && (!a.pool_idx || !a.pool_coef))
-    return pcs_set_einval("pcs_wgrad", "PRO_BWD_POOL needs pool_idx, pool_coef");
   if (a.x_mode == PCS_PRO_BNRELU && (!a.s || !a.t)) return pcs_set_einval("pcs_wgrad", "x BNRELU needs s, t");
-  if (a.dy_colsum && !pcs_wgrad_c5_applicable(a))
-    return pcs_set_einval("pcs_wgrad", "dy_colsum: conv5's R pass only (bf16, RAW dZ, BNRELU x, Cin 128)");
   if (pcs_wgrad_workspace(&a) < 0) return PCS_EINVAL;
   const int ms = a.dtype == PCS_BF16 ? TnCfg<bf16_t>::MS : TnCfg<float>::MS;
   const int64_t rps = rows_per_split_of(a, ms);
@@ -367,11 +357,6 @@ extern "C" int pcs_wgrad(const pcs_wgrad_args *ap, pcs_stream_t stream) {
   else return pcs_set_einval("pcs_wgrad", "bad dtype");
   if (rc) return rc;
   const int64_t nslabs = a.num_scenes * a.splits_per_scene;
-  if (a.dy_colsum) {
-    rc = pcs_reduce_partials(a.partial + nslabs * a.Cout * a.Cin, nslabs, a.Cout, 1.0f, a.dy_colsum, a.Cout, a.Cout,
-                             stream);
-    if (rc) return rc;
-  }
   return pcs_reduce_partials(a.partial, nslabs, (int64_t)a.Cout * a.Cin, 1.0f, a.dW,
                              a.ldw ? a.ldw : a.Cin, a.Cin, stream);
 }

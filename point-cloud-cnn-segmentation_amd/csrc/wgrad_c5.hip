@@ -47,9 +47,6 @@ constexpr int OBW = NB / 128;         // 16-column output tiles of dz5 per wave 
 // slot permutations (the r03 fused_seg.hip, now in git history): dz5 rows chunk c at c ^ ftr(r); y4 rows at c ^ (r & 15);
 // x rows permuted (prow: bits 2 <-> 3) and padded
 
-// S1: also the column sums of dz5 (pcs_wgrad_args.dy_colsum; the opt-in four-wave global_feat
-// kernel's bn5 S1), a separate instantiation so that the default one keeps its registers
-template <bool S1>
 __global__ __launch_bounds__(THREADS) void wgrad_c5_kernel(pcs_wgrad_args a, int64_t rows_per_split) {
   __shared__ __attribute__((aligned(16))) char lds[BYTES];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -120,7 +117,6 @@ __global__ __launch_bounds__(THREADS) void wgrad_c5_kernel(pcs_wgrad_args a, int
     }
   };
 
-  constexpr bool do_s1 = S1;
   // x = relu(bn4(y4)) of step s into x buffer s & 1; rows past the slice -> 0
   const int o_yx = DZB + xrr * YROW + ((xlc ^ (xrr & 15)) << 4);
   const int o_xw = prow(xrr) * XR + xlc * 16;
@@ -133,13 +129,6 @@ __global__ __launch_bounds__(THREADS) void wgrad_c5_kernel(pcs_wgrad_args a, int
     u32x4 out = pack_chunk(v);
     if (xrr >= rem) out = mk_u32x4(0, 0, 0, 0);
     *reinterpret_cast<u32x4 *>(lds + OFF_X + (s & 1) * XB + o_xw) = out;
-    // S1 (dy_colsum): a 17th 16-channel block of ones in the row's pad, zero past the slice,
-    // so that the same transposed read gives the ones fragment with R's row (k) order
-    if constexpr (do_s1) if (xlc < 2) {
-      const uint32_t one = xrr < rem ? 0x3f803f80u : 0u;
-      *reinterpret_cast<u32x4 *>(lds + OFF_X + (s & 1) * XB + prow(xrr) * XR + CIN * 2 + xlc * 16) =
-          mk_u32x4(one, one, one, one);
-    }
   };
 
   // transposed-read offsets (the r03 fused_seg.hip, now in git history's weight-gradient half): dz5 columns 16 (2 wid + ob) +
@@ -155,13 +144,11 @@ __global__ __launch_bounds__(THREADS) void wgrad_c5_kernel(pcs_wgrad_args a, int
   }
   const int o_tx0 = prow(tr0) * XR + 8 * p, o_tx1 = prow(tr1) * XR + 8 * p;   // + u 32 B
 
-  f32x4 acc[OBW][8], acc1[OBW];   // acc1: S1 (every row of the 16 x 16 block is the column sum)
+  f32x4 acc[OBW][8];
 #pragma unroll
-  for (int ob = 0; ob < OBW; ++ob) {
-    acc1[ob] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int ob = 0; ob < OBW; ++ob)
 #pragma unroll
     for (int u = 0; u < 8; ++u) acc[ob][u] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
 
   // ---- prologue: steps 0 .. NST-2 in flight, step 0 landed and transformed
 #pragma unroll
@@ -188,11 +175,6 @@ __global__ __launch_bounds__(THREADS) void wgrad_c5_kernel(pcs_wgrad_args a, int
       for (int ob = 0; ob < OBW; ++ob)
         acc[ob][u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[u & 1], dt[ob], acc[ob][u], 0, 0, 0);
     }
-    if constexpr (do_s1) {
-      const bf16x8 of = tr_frag2(xb + o_tx0 + 8 * 32, xb + o_tx1 + 8 * 32);
-#pragma unroll
-      for (int ob = 0; ob < OBW; ++ob) acc1[ob] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(of, dt[ob], acc1[ob], 0, 0, 0);
-    }
     // step t+1 landed (newer: NST-2 steps' pieces)
     wait_vm<(NST - 2) * LPS>();
     barrier_lds();
@@ -202,13 +184,6 @@ __global__ __launch_bounds__(THREADS) void wgrad_c5_kernel(pcs_wgrad_args a, int
   }
   wait_vm<0>();   // the clamped DMAs past the end
 
-  // ---- this slice's S1 partial (after all slices' R partials): lanes of row group g = 0
-  if (do_s1 && g == 0) {
-    const int64_t nsl = (int64_t)gridDim.x / ncb;
-    float *o1 = a.partial + nsl * Cout * CIN + (int64_t)split * Cout + n0;
-#pragma unroll
-    for (int ob = 0; ob < OBW; ++ob) o1[16 * (OBW * wid + ob) + l16] = acc1[ob][0];
-  }
   // ---- this slice's partial: R[n0 + 16 (OBW wid + ob) + l16][16 u + 4 g .. + 4]
   float *out = a.partial + ((int64_t)split * Cout + n0) * CIN;
 #pragma unroll
@@ -448,10 +423,7 @@ int pcs_wgrad_c5_splits(const pcs_wgrad_args &a) {
 int pcs_wgrad_c5_launch(const pcs_wgrad_args &a, int64_t rows_per_split, hipStream_t s) {
   if (rows_per_split % MS) return pcs_set_einval("pcs_wgrad", "conv5 R: rows per split must be a multiple of 32");
   const int nb = (int)(a.num_scenes * a.splits_per_scene) * (a.Cout / NB);
-  if (a.dy_colsum)
-    hipLaunchKernelGGL(wgrad_c5_kernel<true>, dim3(nb), dim3(THREADS), 0, s, a, rows_per_split);
-  else
-    hipLaunchKernelGGL(wgrad_c5_kernel<false>, dim3(nb), dim3(THREADS), 0, s, a, rows_per_split);
+  hipLaunchKernelGGL(wgrad_c5_kernel, dim3(nb), dim3(THREADS), 0, s, a, rows_per_split);
   PCS_CHECK_LAUNCH();
   return 0;
 }

@@ -32,7 +32,7 @@ def test_library_exports_every_declared_symbol():
     lib.pcs_abi_version.restype = ct.c_int
     hdr = open(os.path.join(REPO, "include", "pcs.h")).read()
     want = int(re.search(r"#define PCS_ABI_VERSION (\d+)", hdr).group(1))
-    assert lib.pcs_abi_version() == want == 2
+    assert lib.pcs_abi_version() == want == 3
     import pcs_amd._lib as L
     assert L.ABI_VERSION == want
 
@@ -73,11 +73,65 @@ def test_geometry_is_scene_aligned():
 def test_fused_dgrad_wgrad_validates_shapes_without_gpu():
     import pcs_amd._lib as L
     lib = L.load()
-    a = L.WgradArgs(num_scenes=1, scene_rows=128, Cout=256, Cin=64, dtype=L.BF16, dy_mode=L.PRO_BWD,
+    a = L.WgradArgs(num_scenes=1, scene_rows=128, Cout=256, Cin=64, dtype=L.BF16, dy_mode=L.PRO_RAW,
                     x_mode=L.PRO_BNRELU)
-    assert lib.pcs_dgrad_wgrad_workspace(ct.byref(a)) < 0
+    assert lib.pcs_dgrad_wgrad_folded_workspace(ct.byref(a)) < 0
     a.Cout = 512
-    assert lib.pcs_dgrad_wgrad_workspace(ct.byref(a)) == a.splits_per_scene * 512 * 64 * 4
+    # include/pcs.h: a slab R [512, 64] | G [64, 64] | S [64] per slice, the summed R | G, then
+    # S_b [B, 64] and cvec [B, 64], all fp32
+    B, slab, rg = 1, 512 * 64 + 64 * 64 + 64, 512 * 64 + 64 * 64
+    nbytes = lib.pcs_dgrad_wgrad_folded_workspace(ct.byref(a))
+    assert a.splits_per_scene >= 1
+    assert nbytes == (B * a.splits_per_scene * slab + rg + 2 * B * 64) * 4
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libpcs.so not built")
+@pytest.mark.parametrize("n,dtype", [(1024, "BF16"), (64, "F32")])
+def test_gemm_rejects_removed_prologue_without_gpu(n, dtype):
+    """Prologue 3 (a hole in the enum since ABI 3) is refused before any operand is looked at:
+    every pointer is NULL, and the error names the prologue, not a missing operand."""
+    import pcs_amd._lib as L
+    lib = L.load()
+    for epi in (L.EPI_RAW, L.EPI_DGRAD):
+        a = L.GemmArgs(num_scenes=1, scene_rows=256, K=n, Ncols=n, dtype=getattr(L, dtype), prologue=3,
+                       epilogue=epi)
+        assert lib.pcs_gemm(ct.byref(a), None) == -1000
+        assert b"prologue" in lib.pcs_last_error()
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libpcs.so not built")
+def test_wgrad_rejects_removed_dy_mode_without_gpu():
+    import pcs_amd._lib as L
+    lib = L.load()
+    a = L.WgradArgs(num_scenes=1, scene_rows=128, Cout=64, Cin=64, dtype=L.BF16, dy_mode=3,
+                    x_mode=L.PRO_BNRELU)
+    assert lib.pcs_wgrad(ct.byref(a), None) == -1000
+    assert b"dy_mode" in lib.pcs_last_error()
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libpcs.so not built")
+@pytest.mark.parametrize("field", ["reserved0", "reserved1", "reserved2"])
+def test_wgrad_rejects_reserved_fields_without_gpu(field):
+    """The three pointer fields removed in ABI 3 keep their place in pcs_wgrad_args; a caller that
+    still fills one gets PCS_EINVAL, not a silent no-op."""
+    import pcs_amd._lib as L
+    lib = L.load()
+    a = L.WgradArgs(num_scenes=1, scene_rows=128, Cout=64, Cin=64, dtype=L.BF16, dy_mode=L.PRO_BWD,
+                    x_mode=L.PRO_BNRELU)
+    assert lib.pcs_wgrad_workspace(ct.byref(a)) > 0
+    setattr(a, field, 1)
+    a.splits_per_scene = 0
+    assert lib.pcs_wgrad_workspace(ct.byref(a)) == -1000
+    assert lib.pcs_wgrad(ct.byref(a), None) == -1000
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libpcs.so not built")
+def test_unfolded_dgrad_wgrad_is_not_exported():
+    import torch  # noqa: F401  (same HIP runtime as the product path)
+    lib = ct.CDLL(LIB)
+    assert hasattr(lib, "pcs_dgrad_wgrad_folded") and hasattr(lib, "pcs_dgrad_wgrad_folded_workspace")
+    assert not hasattr(lib, "pcs_dgrad_wgrad")
+    assert not hasattr(lib, "pcs_dgrad_wgrad_workspace")
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libpcs.so not built")

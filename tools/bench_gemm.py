@@ -35,11 +35,8 @@ def main():
     W = (torch.randn(Nc, K, device=dev) * 0.03).to(torch.bfloat16)
     C = torch.empty(M, Nc, device=dev, dtype=torch.bfloat16)
     vK = lambda lo, sc: torch.rand(K, device=dev) * sc + lo  # noqa: E731
-    s, t, al, be, ga = vK(0.5, 1), vK(-0.1, 0.2), vK(0.5, 1), vK(-1e-3, 2e-3), vK(-1e-3, 2e-3)
+    s, t = vK(0.5, 1), vK(-0.1, 0.2)
     em, er = vK(-0.1, 0.2), vK(1, 1)
-    am = torch.randint(0, N, (B, K), device=dev, dtype=torch.int32) + \
-        (torch.arange(B, device=dev, dtype=torch.int32) * N)[:, None]
-    sp = torch.randn(B, K, device=dev)
     flops = 2.0 * M * K * Nc
 
     def run(name, pro, epi, flags=0, **kw):
@@ -75,10 +72,6 @@ def main():
     ms = timeit(lambda: L.call("pcs_colstats", L.ptr(C), B, N, Nc, L.BF16, cps.value, rpc, L.ptr(st),
                                L.ptr(pl), L.stream_ptr()))
     print(f"{'colstats (stats+pool pass)':44s} {ms:8.3f} ms")
-    pool = dict(pb=be, pc=ga, pool_idx=am, pool_coef=sp)
-    run("dgrad raw (pool prologue)", L.PRO_BWD_POOL, L.EPI_RAW, **pool)
-    run("dgrad fused DGRAD epilogue", L.PRO_BWD_POOL, L.EPI_DGRAD, stats=True, Yp=Y5, es=s, et=t,
-        emean=em, erstd=er, **pool)
     ms = timeit(lambda: L.call("pcs_bnrelu_bwd", L.ptr(C), L.ptr(Y5), None, None, 1.0, L.ptr(s), L.ptr(t),
                                L.ptr(em), L.ptr(er), B, N, Nc, L.BF16, cps.value, rpc, L.ptr(st),
                                L.stream_ptr()))
