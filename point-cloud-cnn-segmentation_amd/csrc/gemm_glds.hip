@@ -187,37 +187,72 @@ __global__ __launch_bounds__(THREADS) void gemm_glds_kernel(pcs_gemm_args a, int
 
   // ---- glds: piece g of wave w covers region rows (2w+g)*8 .. +8; lane -> row +lane/8,
   // LDS slot lane%8, which holds the logical 16-B chunk swz(row, lane%8) of the source row.
-  // Addresses are a uniform (SGPR) base per K-tile plus a 32-bit per-lane byte offset.
-  int qrow[2];
-  uint32_t cbyte[2], boff[2][2];
+  // Addresses are a uniform (SGPR) base per K-tile plus a 32-bit per-lane byte offset, computed
+  // once: aoff / boff[h][g] for the lower / upper A and B regions.
+  uint32_t aoff[2][2], boff[2][2];
 #pragma unroll
   for (int g = 0; g < 2; ++g) {
-    qrow[g] = (2 * wid + g) * 8 + (lane >> 3);
-    cbyte[g] = (uint32_t)swz(qrow[g], lane & 7) * 16u;
+    const int qrow = (2 * wid + g) * 8 + (lane >> 3);
+    const uint32_t cbyte = (uint32_t)swz(qrow, lane & 7) * 16u;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) boff[h][g] = (uint32_t)b_row(h, qrow[g]) * (uint32_t)rowbytes + cbyte[g];
+    for (int h = 0; h < 2; ++h) {
+      aoff[h][g] = (uint32_t)a_row(h, qrow) * (uint32_t)rowbytes + cbyte;
+      boff[h][g] = (uint32_t)b_row(h, qrow) * (uint32_t)rowbytes + cbyte;
+    }
   }
-  // (qseq, tl, kt): K-tile sequence number and its (row tile, K-tile) -- the loop keeps the
-  // latter as counters, so the scalar path has no divisions
-  auto issue = [&](int qseq, int tl, int kt, int region) {
+  // The A source of a K-tile is a scalar pointer (row tile base + 128 kt) that the loop advances
+  // by additions: 128 B to the next K-tile, and once per row tile (pnext(): P tiles up, ntl tiles
+  // back where it wraps) by a step formed at that tile change.  `valid` is the tile's row count
+  // inside the scene (BM except on a scene's last tile).
+  const int rows_left = (int)pcs_min64((int64_t)ntl * BM, scene_end - row0);   // of the chunk
+  auto valid_of = [&](int pt) { return min(BM, rows_left - pt * BM); };
+  // the K-tile after (pt, kt) at sb: the pointer moves, (pt, kt) are advanced by the caller.
+  // The two steps of a tile change are formed where they are taken, behind empty asm
+  // statements: as loop invariants hipcc keeps them in four SGPRs through the loop, which the
+  // forward (already spilling SGPRs) does not have; one scalar multiply per row tile, two at a
+  // wrap, instead.  DGRAD visits the tiles in order (P == 1, a constant step); its only wrap is
+  // past the chunk's last K-tile, whose pointer is never used (issue_a's qseq >= total).
+  auto a_next = [&](const char *sb, int pt, int kt) {
+    if (kt + 1 != nks) return sb + 128;
+    int np = P;
+    if (MODE == MODE_FWD) asm volatile("" : "+s"(np));
+    // P <= 97 tiles of at most 512 KB (K <= 1024), less the nks - 1 K-tiles walked: 32 bits
+    sb += (uint32_t)np * BM * (uint32_t)rowbytes - ((uint32_t)rowbytes - 128u);
+    if (MODE == MODE_FWD && pt + P >= ntl) {
+      uint32_t n = (uint32_t)ntl;
+      asm volatile("" : "+s"(n));
+      sb -= ((uint64_t)n * (uint32_t)rowbytes) * BM;
+    }
+    return sb;
+  };
+  // qseq: K-tile sequence number; sb / valid: its A source and row count (A regions only)
+  auto issue_a = [&](int qseq, const char *sb, int valid, int region) {
     if (qseq >= total) return;   // nothing left to prefetch: the loop's tail waits shrink
                                  // to match (see the phase waits below)
     char *dst = lds + (qseq & 1) * KBUF + region * REG;
-    if (region < 2) {
-      const int64_t rb = row0 + (int64_t)tl * BM;
-      const int valid = (int)pcs_min64(BM, scene_end - rb);
-      const char *sb = Ab + rb * rowbytes + kt * 128;
+    if (valid == BM) {           // uniform
+#pragma unroll
+      for (int g = 0; g < 2; ++g) glds16(sb, aoff[region][g], dst + (2 * wid + g) * 1024);
+    } else {
+      // a scene's last tile: rows past the scene are clamped to its last row.  The offsets are
+      // recomputed from the thread id here (behind an empty asm, so that they are not hoisted
+      // out of the loop into registers the accumulators need)
+      int t = tid;
+      asm volatile("" : "+v"(t));
 #pragma unroll
       for (int g = 0; g < 2; ++g) {
-        const uint32_t tr = (uint32_t)min(a_row(region, qrow[g]), valid - 1);   // rows past the scene: clamped
-        glds16(sb, tr * (uint32_t)rowbytes + cbyte[g], dst + (2 * wid + g) * 1024);
+        const int qrow = (2 * wid + g) * 8 + ((t & 63) >> 3);
+        const uint32_t tr = (uint32_t)min(a_row(region, qrow), valid - 1);
+        glds16(sb, tr * (uint32_t)rowbytes + (uint32_t)swz(qrow, t & 7) * 16u, dst + (2 * wid + g) * 1024);
       }
-    } else {
-      const char *sb = Wb + kt * 128;
-#pragma unroll
-      for (int g = 0; g < 2; ++g)
-        glds16(sb, boff[region - 2][g], dst + (2 * wid + g) * 1024);
     }
+  };
+  auto issue_b = [&](int qseq, int kt, int region) {
+    if (qseq >= total) return;
+    char *dst = lds + (qseq & 1) * KBUF + region * REG;
+    const char *sb = Wb + kt * 128;
+#pragma unroll
+    for (int g = 0; g < 2; ++g) glds16(sb, boff[region - 2][g], dst + (2 * wid + g) * 1024);
   };
 
   // ---- fragment reads (ds_read_b128 of the swizzled 16-B chunks): bf16 16x16x32 takes
@@ -338,8 +373,10 @@ __global__ __launch_bounds__(THREADS) void gemm_glds_kernel(pcs_gemm_args a, int
 
   // ---- prologue: K-tile 0 landed; A-lo, B-lo, B-hi of K-tile 1 in flight
   const int tl1 = nks == 1 ? pnext(0) : 0, kt1 = nks == 1 ? 0 : 1;   // K-tile 1 (row tile permuted)
-  issue(0, 0, 0, 0); issue(0, 0, 0, 1); issue(0, 0, 0, 2); issue(0, 0, 0, 3);
-  issue(1, tl1, kt1, 0); issue(1, tl1, kt1, 2); issue(1, tl1, kt1, 3);
+  const char *sa0 = Ab + row0 * rowbytes;   // A source of K-tile 0; sa1: of K-tile qs + 1
+  const char *sa1 = a_next(sa0, 0, 0);
+  issue_a(0, sa0, valid_of(0), 0); issue_a(0, sa0, valid_of(0), 1); issue_b(0, 0, 2); issue_b(0, 0, 3);
+  issue_a(1, sa1, valid_of(tl1), 0); issue_b(1, kt1, 2); issue_b(1, kt1, 3);
   wait_vm<6>();
   barrier_raw();
 
@@ -358,7 +395,8 @@ __global__ __launch_bounds__(THREADS) void gemm_glds_kernel(pcs_gemm_args a, int
 
   // (row tile, K-tile) of qs and of qs + 1; pcur / pa: their row tiles in visiting order
   int kt = 0, tcur = 0, ta = 0, ka = 0, pcur = 0, pa = 0;
-  for (int qs = 0; qs < total; ++qs, kt = ka, tcur = ta, pcur = pa) {
+  const char *sa2 = sa1;   // A source of K-tile qs + 2
+  for (int qs = 0; qs < total; ++qs, kt = ka, tcur = ta, pcur = pa, sa1 = sa2) {
     const int buf = qs & 1;
     // (row tile, K-tile) of qs + 1 and qs + 2
     const bool w1 = kt + 1 == nks;
@@ -368,6 +406,7 @@ __global__ __launch_bounds__(THREADS) void gemm_glds_kernel(pcs_gemm_args a, int
     const bool w2 = ka + 1 == nks;
     const int kb = w2 ? 0 : ka + 1;
     const int pb = w2 ? pnext(pa) : pa;
+    sa2 = a_next(sa1, pa, ka);
     // phase 1: (rows lo, cols lo); restage A-hi of K-tile qs+1
     const bool xmask = MODE == MODE_DGRAD && (unsigned)(kt - kq0) < NKQ;   // uniform
     u32x4 mv0, mv1;
@@ -377,11 +416,11 @@ __global__ __launch_bounds__(THREADS) void gemm_glds_kernel(pcs_gemm_args a, int
       mask_load(buf, 0, mv0, mv1);
       mask_bits(0, kt - kq0, tcur & 1, mv0, mv1);
     }
-    issue(qs + 1, pa, ka, 1);
+    issue_a(qs + 1, sa1, valid_of(pa), 1);
     // every counted wait assumes the five regions issued after the one it retires are in
-    // flight; on a chunk's last two K-tiles issue() skips loads, so the counts shrink to the
-    // regions actually issued (phase 1 retires B-hi(qs): newer are A-hi(qs) and, unless qs is
-    // the last K-tile, the four regions of qs+1)
+    // flight; on a chunk's last two K-tiles issue_a() / issue_b() skip loads, so the counts
+    // shrink to the regions actually issued (phase 1 retires B-hi(qs): newer are A-hi(qs) and,
+    // unless qs is the last K-tile, the four regions of qs+1)
     if (qs + 1 < total) wait_vm<10>(); else wait_vm<2>();
     wait_lgkm0();
     barrier_raw();
@@ -389,7 +428,7 @@ __global__ __launch_bounds__(THREADS) void gemm_glds_kernel(pcs_gemm_args a, int
     barrier_raw();
     // phase 2: (lo, hi); restage A-lo of K-tile qs+2
     read_b(buf, 3, 2);
-    issue(qs + 2, pb, kb, 0);
+    issue_a(qs + 2, sa2, valid_of(pb), 0);
     // retires A-hi(qs): newer are the four regions of qs+1 and A-lo(qs+2)
     if (qs + 2 < total) wait_vm<10>(); else if (qs + 1 < total) wait_vm<8>(); else wait_vm<0>();
     wait_lgkm0();
@@ -398,7 +437,7 @@ __global__ __launch_bounds__(THREADS) void gemm_glds_kernel(pcs_gemm_args a, int
     barrier_raw();
     // phase 3: (hi, lo); restage B-lo of K-tile qs+2
     read_a(buf, 1);
-    issue(qs + 2, pb, kb, 2);
+    issue_b(qs + 2, kb, 2);
     wait_lgkm0();
     barrier_raw();
     mfma_quad(4, 0);
@@ -410,7 +449,7 @@ __global__ __launch_bounds__(THREADS) void gemm_glds_kernel(pcs_gemm_args a, int
       mask_load(buf, 1, mv0, mv1);
       mask_bits(1, kt - kq0, tcur & 1, mv0, mv1);
     }
-    issue(qs + 2, pb, kb, 3);
+    issue_b(qs + 2, kb, 3);
     // retires A-lo(qs+1), B-lo(qs+1): newer are B-hi(qs+1), A-hi(qs+1) and three of qs+2
     if (qs + 2 < total) wait_vm<10>(); else if (qs + 1 < total) wait_vm<4>(); else wait_vm<0>();
     barrier_raw();
@@ -427,7 +466,7 @@ __global__ __launch_bounds__(THREADS) void gemm_glds_kernel(pcs_gemm_args a, int
 
     // ===================== epilogue of row tile tcur (rows of tile pcur) =====================
     const int64_t rb = row0 + (int64_t)pcur * BM;
-    const int valid = (int)pcs_min64(BM, scene_end - rb);
+    const int valid = valid_of(pcur);
     const int nvw = max(0, min(128, valid - wm * 128));   // valid rows of this wave's half
     // lane's columns c(j, r) = wn*64 + j*16 + 4*lg + r; rows m(i) = wm*128 + i*16 + lr
     uint32_t rowok = 0;   // bit i: row m(i) is a row of the scene
