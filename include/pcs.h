@@ -147,6 +147,19 @@ int pcs_conv1_fwd(const pcs_gemm_args *args, pcs_stream_t stream);
  * dy = alpha*dZ + beta + gamma*Y (PCS_PRO_BWD) or dZ as stored (PCS_PRO_RAW), x = pro_x(X)
  * (PCS_PRO_BNRELU or PCS_PRO_RAW).  The reduction over M is split into scene-aligned slices
  * whose fp32 partials are summed in a fixed order (deterministic).
+ *
+ * Supported (dy_mode, x_mode) pairs; any other is refused with PCS_EINVAL:
+ *   (PCS_PRO_BWD, PCS_PRO_BNRELU)  with or without x_mask
+ *   (PCS_PRO_BWD, PCS_PRO_RAW)
+ *   (PCS_PRO_RAW, PCS_PRO_BNRELU)  with or without x_mask
+ *   (PCS_PRO_RAW, PCS_PRO_RAW)     refused
+ * (x_mask is read only with x_mode PCS_PRO_BNRELU.)  Kernels by shape class:
+ *   - fp32, and bf16 not named below or with PCS_FLAG_GENERIC: wgrad_kernel (csrc/gemm_tn.hip),
+ *     a 128- or 64-wide tile per side by Cout % 128 and Cin % 128; 16 (fp32) or 64 (bf16) rows a step;
+ *   - bf16, Cout % 256 == 0 and Cin % 256 == 0, (BWD, BNRELU): wgrad_big_kernel (csrc/gemm_big_tn.hip);
+ *   - bf16, Cin == 128, Cout % 256 == 0, (RAW, BNRELU) without x_mask: the LDS-DMA stream of
+ *     csrc/wgrad_c5.hip (conv5's R).
+ * In bf16 dy and x are rounded to bf16 as they are staged: after the affine step, after the keep scale.
  */
 typedef struct {
   int64_t num_scenes, scene_rows;
