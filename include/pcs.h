@@ -822,6 +822,41 @@ int pcs_rows_interp(const void *X, int32_t xdtype, const int32_t *idx, const flo
 int pcs_rows_segsum(const void *X, int32_t xdtype, const int32_t *src, const float *w, const int64_t *seg_off,
                     const float *scale, int64_t M, int32_t C, void *Y, int32_t ydtype, pcs_stream_t stream);
 
+/*
+ * BatchNorm (+ residual) (+ ReLU) on the occupied-voxel path (csrc/sparse_bn.hip; build-defined, the
+ * numpy statement is tests/sparse_norm_refs.py): the layer between the sparse convolutions, forward
+ * and backward, on a flat row array X [V, C] without scene structure.  X (xdtype) and the output
+ * side Y / R / dY / DZ (ydtype) are each PCS_F32 or PCS_BF16; C % 8 == 0 when either side is bf16,
+ * else C % 4 == 0; C <= 1024.  fp32 arithmetic, no atomics, fixed summation order.
+ * pcs_sparse_bn_geometry: the row blocks of the two reductions: returns rows_per_block =
+ *   64 * ceil(V / (64 * 2048)) (at least 64) and *num_blocks = ceil(V / rows_per_block) <= 2048 (0
+ *   when V == 0); no block is empty.  It takes no dtype: C % 4 == 0, 4 <= C <= 1024.
+ * pcs_sparse_bn_stats: stats [num_blocks][C][2] = each block's (mean, M2) of X's columns, the
+ *   partials of pcs_bn_fwd_finalize(stats, 1, V, C, num_blocks, rows_per_block, ...), which yields
+ *   mean, rstd, scale, shift and the running-buffer update (eval: pcs_bn_eval_coefs).
+ * pcs_sparse_bn_apply: Y = act(fma(X, scale[c], shift[c]) (+ R)), act = relu (a NaN propagates)
+ *   when relu != 0, else the identity; R NULL or [V, C] in ydtype.
+ * pcs_sparse_bn_bwd_reduce: dz = relu ? (Y > 0 ? dY : 0) : dY stored to DZ [V, C] in ydtype (also
+ *   the residual's gradient; Y and DZ may be NULL when relu == 0) and stats [num_blocks][C][2] =
+ *   each block's (S1 = sum dz, S2 = sum dz * (X - mean[c]) * rstd[c]), the partials of
+ *   pcs_bn_bwd_finalize(stats, 1, V, C, num_blocks, ...), which yields alpha, beta_c, gamma_c,
+ *   dgamma and dbeta.
+ * pcs_sparse_bn_bwd_apply: dX = fma(alpha[c], DZ, fma(gamma_c[c], X, beta_c[c])) in xdtype.
+ * A geometry other than pcs_sparse_bn_geometry's is accepted when its blocks tile [0, V) and none
+ * is empty.  Every output row is stored exactly once; V == 0 returns 0 without a launch.
+ */
+int64_t pcs_sparse_bn_geometry(int64_t V, int32_t C, int32_t *num_blocks);
+int pcs_sparse_bn_stats(const void *X, int32_t xdtype, int64_t V, int32_t C, int32_t num_blocks,
+                        int64_t rows_per_block, float *stats, pcs_stream_t stream);
+int pcs_sparse_bn_apply(const void *X, int32_t xdtype, const void *R, const float *scale, const float *shift,
+                        int32_t relu, int64_t V, int32_t C, void *Y, int32_t ydtype, pcs_stream_t stream);
+int pcs_sparse_bn_bwd_reduce(const void *dY, const void *Y, int32_t ydtype, const void *X, int32_t xdtype,
+                             const float *mean, const float *rstd, int32_t relu, int64_t V, int32_t C,
+                             int32_t num_blocks, int64_t rows_per_block, void *DZ, float *stats, pcs_stream_t stream);
+int pcs_sparse_bn_bwd_apply(const void *DZ, int32_t ydtype, const void *X, int32_t xdtype, const float *alpha,
+                            const float *beta_c, const float *gamma_c, int64_t V, int32_t C, void *dX,
+                            pcs_stream_t stream);
+
 /* Build-time identification and error string. pcs_abi_version() returns PCS_ABI_VERSION,
  * bumped with every change to an argument struct's layout or an entry point's signature
  * (2: pcs_gemm_args gained `gram`, the w4 entry points were removed; 3: prologue 3, three

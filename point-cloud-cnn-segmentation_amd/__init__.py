@@ -32,6 +32,9 @@ _LAZY = {
     "point_voxel_map": ("pointvoxel", "point_voxel_map"),
     "voxel_mean": ("pointvoxel", "voxel_mean"),
     "devoxelize": ("pointvoxel", "devoxelize"),
+    "sparse_batch_norm": ("sparse_norm", "sparse_batch_norm"),
+    "SparseBatchNorm": ("sparse_norm", "SparseBatchNorm"),
+    "SparseResBlock": ("sparse_norm", "SparseResBlock"),
 }
 
 

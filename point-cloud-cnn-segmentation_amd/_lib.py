@@ -164,6 +164,12 @@ SIGNATURES = [
                                        _vp, _vp]),
     ("pcs_rows_interp", ct.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp]),
     ("pcs_rows_segsum", ct.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp]),
+    ("pcs_sparse_bn_geometry", _i64, [_i64, _i32, ct.POINTER(_i32)]),
+    ("pcs_sparse_bn_stats", ct.c_int, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp]),
+    ("pcs_sparse_bn_apply", ct.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp]),
+    ("pcs_sparse_bn_bwd_reduce", ct.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _vp,
+                                            _vp, _vp]),
+    ("pcs_sparse_bn_bwd_apply", ct.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     ("pcs_gram_workspace", _i64, [_i64, _i64, _i32, _i32, ct.POINTER(_i32)]),
     ("pcs_gram", ct.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     ("pcs_pool_rows_add", ct.c_int, [_vp, _i32, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32,
