@@ -250,6 +250,16 @@ def call(name, *args):
     return rc
 
 
+def workspace(name, *args) -> int:
+    """The value of a size query (a *_workspace, *_capacity or *_geometry function); a negative
+    return raises PcsError with the library's message."""
+    lib = load()
+    n = int(getattr(lib, name)(*args))
+    if n < 0:
+        raise PcsError(lib.pcs_last_error().decode())
+    return n
+
+
 def ptr(t):
     """Raw device pointer of a tensor (None -> NULL)."""
     return None if t is None else t.data_ptr()

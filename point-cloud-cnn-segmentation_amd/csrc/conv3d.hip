@@ -11,14 +11,20 @@
 // kernel serves the forward and the input gradient of both; the weight gradient uses the
 // forward's index map.
 //
-// conv3d_kernel: implicit GEMM, rows = output voxels, columns = output channels, k = (tap,
-// 32-channel slice).  A k-step gathers the 64 rows' input voxels of one tap into LDS (zero rows
-// off the grid or off the stride lattice): the 27-tap stencil is 27 shifted gathers of the same
-// channels-last rows, so after the first tap the re-reads come from L2.  The next k-step is
-// loaded into registers while the MFMAs of this one run; one barrier per k-step.
-// conv3d_wgrad_kernel: dW_t = dY^T X_t over output voxels in 32-voxel k-steps, both operands
-// staged row-major and read transposed (ds_read_b64_tr_b16) so the MFMA's k runs over voxels;
-// split over voxel slices with fp32 partials summed in a fixed order (deterministic).
+// Every gather convolution in this file is one of two loops with a different row index:
+//   gather_gemm_tile + store_tile: the forward / input-gradient implicit GEMM, rows = output rows,
+//     columns = output channels, k = (tap, channel slice).  A k-step gathers the tile's input rows
+//     of one tap into LDS (zero rows where there is none): a stencil is shifted gathers of the
+//     same channels-last rows, so after the first tap the re-reads come from L2.  Instantiated by
+//     conv3d_kernel (rows from the grid geometry), sparse_conv_kernel (rows from a neighbour map,
+//     only the taps a tile meets), pair_gemm_kernel and pair_rows_kernel (rows from one tap's
+//     pair list; the first stores raw products, the second scatters through pair_out).
+//   wgrad_tile + store_wgrad_tile: dW_t = dY^T X_t over rows in 32-row k-steps, both operands
+//     staged row-major and read transposed (ds_read_b64_tr_b16) so the MFMA's k runs over rows;
+//     split over row slices with fp32 partials summed in a fixed order (deterministic).
+//     Instantiated by conv3d_wgrad_kernel, sparse_wgrad_kernel (up to TG taps share one dY image)
+//     and pair_wgrad_kernel (one tap's pair list).
+// The 3x3x3 stride-1 stencil has its own halo-staged kernels (stencil3_kernel, stencil3_wgrad_kernel).
 #include "kernel_prims.h"
 
 namespace {
@@ -111,17 +117,25 @@ PCS_DEV void decode_class(const PClass &q, int64_t u, int &b, int &z, int &y, in
   b = (int)(u / q.nz);
 }
 
-// BMT = 64 or 128 output voxels per tile (4 waves as 2 x 2: wave tile BMT/2 x BNT/2); KST = 32 or
-// 64 input channels per k-step (64: whole 128-B voxel rows per load, 2x the MFMAs per barrier);
-// BNT = 64 or 32 output channels per tile (32: a 32-channel U-Net level without zero channels)
-template <int BMT, int KST, bool OUT_BF16, int BNT = BN>
-__global__ __launch_bounds__(THREADS) void conv3d_kernel(pcs_conv3d_geom g, const bf16_t *__restrict__ X,
-                                                         const bf16_t *__restrict__ W, const float *__restrict__ bias,
-                                                         void *__restrict__ Y, int64_t M) {
+// ---- The gather-GEMM tile loop of every forward kernel here (conv3d_kernel, sparse_conv_kernel,
+// pair_gemm_kernel, pair_rows_kernel): acc = sum over the tile's nrun taps j of W[wtap(j)] X[in_row],
+// fp32, for BMT rows and the BNT output channels from n0.  The kernels differ only in where a row
+// comes from: in_row(h, r, j) is the input row of staged row r = srow + RPP h (this thread's h-th
+// staging pass) at run-tap j, or -1 for a zero row; wtap(j) is the weight tap of run-tap j.
+// BMT = 64 or 128 rows per tile (4 waves as 2 x 2: wave tile BMT/2 x BNT/2); KST = 32 or 64 input
+// channels per k-step (64: whole 128-B rows per load, 2x the MFMAs per barrier); BNT = 64 or 32
+// output channels per tile (32: a 32-channel U-Net level without zero channels).  A k-step stages
+// the rows of one (tap, channel slice) through registers into swizzled LDS; the next k-step is loaded
+// while the MFMAs of this one run, one barrier per k-step.  Lane (lr, lg) of wave (wr, wc) ends
+// with row wr BMT/2 + 16 i + lr, channels n0 + wc BNT/2 + 16 j + 4 lg .. + 3 in acc[i][j].
+template <int BMT, int KST, int BNT, class RowF, class TapF>
+PCS_DEV void gather_gemm_tile(const bf16_t *__restrict__ X, int Cin, const bf16_t *__restrict__ W, int taps, int n0,
+                              int nrun, RowF in_row, TapF wtap, f32x4 (&acc_out)[BMT / 32][BNT / 32]) {
   constexpr int RB = KST * 2;          // LDS row bytes
   constexpr int CPR = KST / 8;         // 16-B chunks per row
   constexpr int RPP = THREADS / CPR;   // rows staged per pass
-  constexpr int HA = BMT / RPP, HB = (BNT + RPP - 1) / RPP;   // (BNT < RPP: the first BNT rows' threads)
+  constexpr int HA = BMT / RPP, HB = (BNT + RPP - 1) / RPP;
+  constexpr bool WPART = BNT % RPP != 0;   // BNT < RPP (32 channels, 32-deep k-steps): the first BNT rows' threads
   constexpr int TI = BMT / 32;         // 16-row MFMA tiles per wave
   constexpr int TJ = BNT / 32;         // 16-channel MFMA tiles per wave
   constexpr int KK = KST / 32;         // MFMA k-steps per k-step
@@ -129,57 +143,25 @@ __global__ __launch_bounds__(THREADS) void conv3d_kernel(pcs_conv3d_geom g, cons
   auto swzf = [](int row, int slot) { return KST == 32 ? cswz(row, slot) : (slot ^ ((row >> 1) & 7)); };
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
-  // class mode (transposed, stride 2): blockIdx.x = tile * 8 + class, rows index the class sub-grid
-  const bool cm = g.transposed && g.s == 2;
-  PClass pc{};
-  int64_t Mrows = M;
-  int64_t m0 = (int64_t)blockIdx.x * BMT;
-  if (cm) {
-    pc = pclass(g, blockIdx.x & 7);
-    Mrows = g.B * pc.nz * pc.ny * pc.nx;
-    m0 = (int64_t)(blockIdx.x >> 3) * BMT;
-    if (m0 >= Mrows) return;   // uniform: this class has fewer tiles than the largest
-  }
-  const int n0 = blockIdx.y * BNT;
   const int srow = tid / CPR, q = tid % CPR;   // staging: chunk q of rows srow + RPP h
-  bool rv[HA];
-  int vb[HA], vz[HA], vy[HA], vx[HA];
-#pragma unroll
-  for (int h = 0; h < HA; ++h) {
-    const int64_t u = m0 + srow + RPP * h;
-    rv[h] = u < Mrows;
-    vb[h] = vz[h] = vy[h] = vx[h] = 0;
-    if (rv[h]) {
-      if (cm) decode_class(pc, u, vb[h], vz[h], vy[h], vx[h]);
-      else decode(g, u, vb[h], vz[h], vy[h], vx[h]);
-    }
-  }
-  const int k = g.k, taps = k * k * k, cps = g.Cin / KST;
-  const int ctaps = cm ? pc.ntz * pc.nty * pc.ntx : taps;   // taps this tile runs
-  const int nks = ctaps * cps;
-  const bf16_t *wrow = W + (int64_t)(n0 + srow) * taps * g.Cin + q * 8;
-  const int64_t wstep = (int64_t)RPP * taps * g.Cin;
+  const int nks = nrun * (Cin / KST);
+  const bf16_t *wrow = W + (int64_t)(n0 + srow) * taps * Cin + q * 8;
+  const int64_t wstep = (int64_t)RPP * taps * Cin;
 
   u32x4 ra[HA], rb[HB];
-  auto load = [&](int ks) {
-    const int j = ks / cps, c0 = (ks - j * cps) * KST;
-    int dz, dy, dx;
-    if (cm) {
-      dz = pc.tz0 + 2 * (j / (pc.nty * pc.ntx));
-      dy = pc.ty0 + 2 * ((j / pc.ntx) % pc.nty);
-      dx = pc.tx0 + 2 * (j % pc.ntx);
-    } else {
-      dz = j / (k * k); dy = (j / k) % k; dx = j % k;
-    }
-    const int t = (dz * k + dy) * k + dx;
+  int lj = 0, lc = 0;   // the next k-step to load: run-tap lj, channels lc .. lc + KST (no division per k-step)
+  auto load = [&]() {
+    const int t = wtap(lj);
 #pragma unroll
     for (int h = 0; h < HA; ++h) {
-      const int64_t iv = rv[h] ? in_voxel(g, vb[h], vz[h], vy[h], vx[h], dz, dy, dx) : -1;
-      ra[h] = iv >= 0 ? *reinterpret_cast<const u32x4 *>(X + iv * g.Cin + c0 + q * 8) : mk_u32x4(0, 0, 0, 0);
+      const int64_t iv = in_row(h, srow + RPP * h, lj);
+      ra[h] = iv >= 0 ? *reinterpret_cast<const u32x4 *>(X + iv * Cin + lc + q * 8) : mk_u32x4(0, 0, 0, 0);
     }
 #pragma unroll
     for (int h = 0; h < HB; ++h)
-      if (srow + RPP * h < BNT) rb[h] = *reinterpret_cast<const u32x4 *>(wrow + h * wstep + (int64_t)t * g.Cin + c0);
+      if (!WPART || srow + RPP * h < BNT) rb[h] = *reinterpret_cast<const u32x4 *>(wrow + h * wstep + (int64_t)t * Cin + lc);
+    lc += KST;
+    if (lc == Cin) { lc = 0; ++lj; }
   };
   auto stage = [&](int buf) {
     char *tA = lds[buf], *tB = lds[buf] + BMT * RB;
@@ -191,23 +173,23 @@ __global__ __launch_bounds__(THREADS) void conv3d_kernel(pcs_conv3d_geom g, cons
 #pragma unroll
     for (int h = 0; h < HB; ++h) {
       const int r = srow + RPP * h;
-      if (r < BNT) *reinterpret_cast<u32x4 *>(tB + r * RB + swzf(r, q) * 16) = rb[h];
+      if (!WPART || r < BNT) *reinterpret_cast<u32x4 *>(tB + r * RB + swzf(r, q) * 16) = rb[h];
     }
   };
 
-  f32x4 acc[TI][TJ];
+  f32x4 acc[TI][TJ];   // (locals, handed over once at the end: see wgrad_tile)
 #pragma unroll
   for (int i = 0; i < TI; ++i)
 #pragma unroll
     for (int j = 0; j < TJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (nks > 0) {
-    load(0);
+    load();
     stage(0);
   }
   __syncthreads();
   for (int ks = 0; ks < nks; ++ks) {
     const int buf = ks & 1;
-    if (ks + 1 < nks) load(ks + 1);
+    if (ks + 1 < nks) load();
     const char *tA = lds[buf], *tB = lds[buf] + BMT * RB;
 #pragma unroll
     for (int kk = 0; kk < KK; ++kk) {
@@ -222,7 +204,7 @@ __global__ __launch_bounds__(THREADS) void conv3d_kernel(pcs_conv3d_geom g, cons
         const int r = wc * (BNT / 2) + j * 16 + lr;
         bw[j] = *reinterpret_cast<const bf16x8 *>(tB + r * RB + swzf(r, kk * 4 + lg) * 16);
       }
-      // W rows as the MFMA A operand: each lane ends with 4 consecutive output channels of one voxel
+      // W rows as the MFMA A operand: each lane ends with 4 consecutive output channels of one row
 #pragma unroll
       for (int i = 0; i < TI; ++i)
 #pragma unroll
@@ -231,18 +213,26 @@ __global__ __launch_bounds__(THREADS) void conv3d_kernel(pcs_conv3d_geom g, cons
     if (ks + 1 < nks) stage(buf ^ 1);   // buf ^ 1 was last read before the previous barrier
     __syncthreads();
   }
+#pragma unroll
+  for (int i = 0; i < TI; ++i)
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) acc_out[i][j] = acc[i][j];
+}
 
+// The forward epilogue on gather_gemm_tile's accumulators: Y[out_row(r)][n0 ..] = acc + bias, 4
+// channels of one row per store (bf16 or fp32); out_row(r) is the output row of tile row r, or -1
+// to skip it.
+template <int BMT, int BNT, bool OUT_BF16, class RowF>
+PCS_DEV void store_tile(const f32x4 (&acc)[BMT / 32][BNT / 32], RowF out_row, int n0, int Cout,
+                        const float *__restrict__ bias, void *__restrict__ Y) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
 #pragma unroll
-  for (int i = 0; i < TI; ++i) {
-    int64_t uo = m0 + wr * (BMT / 2) + i * 16 + lr;
-    if (uo >= Mrows) continue;
-    if (cm) {   // class row -> output voxel
-      int ob, oz, oy, ox;
-      decode_class(pc, uo, ob, oz, oy, ox);
-      uo = (((int64_t)ob * g.Do + oz) * g.Ho + oy) * g.Wo + ox;
-    }
+  for (int i = 0; i < BMT / 32; ++i) {
+    const int64_t uo = out_row(wr * (BMT / 2) + i * 16 + lr);
+    if (uo < 0) continue;
 #pragma unroll
-    for (int j = 0; j < TJ; ++j) {
+    for (int j = 0; j < BNT / 32; ++j) {
       const int co = n0 + wc * (BNT / 2) + j * 16 + 4 * lg;
       float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
       if (bias) {
@@ -250,13 +240,73 @@ __global__ __launch_bounds__(THREADS) void conv3d_kernel(pcs_conv3d_geom g, cons
         v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
       }
       if constexpr (OUT_BF16) {
-        *reinterpret_cast<uint2 *>(reinterpret_cast<bf16_t *>(Y) + uo * g.Cout + co) =
+        *reinterpret_cast<uint2 *>(reinterpret_cast<bf16_t *>(Y) + uo * Cout + co) =
             make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
       } else {
-        *reinterpret_cast<float4 *>(reinterpret_cast<float *>(Y) + uo * g.Cout + co) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4 *>(reinterpret_cast<float *>(Y) + uo * Cout + co) = make_float4(v[0], v[1], v[2], v[3]);
       }
     }
   }
+}
+
+// The dense gather: rows = output voxels, zero rows off the grid or off the stride lattice
+template <int BMT, int KST, bool OUT_BF16, int BNT = BN>
+__global__ __launch_bounds__(THREADS) void conv3d_kernel(pcs_conv3d_geom g, const bf16_t *__restrict__ X,
+                                                         const bf16_t *__restrict__ W, const float *__restrict__ bias,
+                                                         void *__restrict__ Y, int64_t M) {
+  constexpr int RPP = THREADS / (KST / 8), HA = BMT / RPP;   // gather_gemm_tile's staging passes
+  // class mode (transposed, stride 2): blockIdx.x = tile * 8 + class, rows index the class sub-grid
+  const bool cm = g.transposed && g.s == 2;
+  PClass pc{};
+  int64_t Mrows = M;
+  int64_t m0 = (int64_t)blockIdx.x * BMT;
+  if (cm) {
+    pc = pclass(g, blockIdx.x & 7);
+    Mrows = g.B * pc.nz * pc.ny * pc.nx;
+    m0 = (int64_t)(blockIdx.x >> 3) * BMT;
+    if (m0 >= Mrows) return;   // uniform: this class has fewer tiles than the largest
+  }
+  const int srow = threadIdx.x / (KST / 8);
+  bool rv[HA];
+  int vb[HA], vz[HA], vy[HA], vx[HA];
+#pragma unroll
+  for (int h = 0; h < HA; ++h) {
+    const int64_t u = m0 + srow + RPP * h;
+    rv[h] = u < Mrows;
+    vb[h] = vz[h] = vy[h] = vx[h] = 0;
+    if (rv[h]) {
+      if (cm) decode_class(pc, u, vb[h], vz[h], vy[h], vx[h]);
+      else decode(g, u, vb[h], vz[h], vy[h], vx[h]);
+    }
+  }
+  const int k = g.k, taps = k * k * k, n0 = blockIdx.y * BNT;
+  // run-tap j of this tile: every tap, or every second one from the class's first (without a
+  // branch, so that the decodes of one k-step's in_row and wtap calls fold into one)
+  const int ts = cm ? 2 : 1, tny = cm ? pc.nty : k, tnx = cm ? pc.ntx : k;
+  auto tap3 = [&](int j, int &dz, int &dy, int &dx) {
+    dz = pc.tz0 + ts * (j / (tny * tnx)); dy = pc.ty0 + ts * ((j / tnx) % tny); dx = pc.tx0 + ts * (j % tnx);
+  };
+  auto in_row = [&](int h, int, int j) -> int64_t {
+    int dz, dy, dx;
+    tap3(j, dz, dy, dx);
+    return rv[h] ? in_voxel(g, vb[h], vz[h], vy[h], vx[h], dz, dy, dx) : -1;
+  };
+  auto wtap = [&](int j) {
+    int dz, dy, dx;
+    tap3(j, dz, dy, dx);
+    return (dz * k + dy) * k + dx;
+  };
+  f32x4 acc[BMT / 32][BNT / 32];
+  gather_gemm_tile<BMT, KST, BNT>(X, g.Cin, W, taps, n0, cm ? pc.ntz * pc.nty * pc.ntx : taps, in_row, wtap, acc);
+  auto out_row = [&](int r) -> int64_t {
+    const int64_t uo = m0 + r;
+    if (uo >= Mrows) return -1;
+    if (!cm) return uo;
+    int ob, oz, oy, ox;   // class row -> output voxel
+    decode_class(pc, uo, ob, oz, oy, ox);
+    return (((int64_t)ob * g.Do + oz) * g.Ho + oy) * g.Wo + ox;
+  };
+  store_tile<BMT, BNT, OUT_BF16>(acc, out_row, n0, g.Cout, bias, Y);
 }
 
 // ---- 3x3x3 stride-1 stencil (both forms) with the input block's halo staged in LDS once per
@@ -412,15 +462,101 @@ PCS_DEV bf16x8 wfrag(const char *img, int cb, int lane) {
 // in class mode, where the dx taps meet different voxel sets)
 constexpr int TG = 3;
 
-// COT x CIT = the workgroup's (co, ci) tile, 64 or 32 each (a 32-channel level stages half rows)
+// The k-over-voxels loop of every weight-gradient kernel here (conv3d_wgrad_kernel,
+// sparse_wgrad_kernel, pair_wgrad_kernel): acc[a] += dY^T X_a over nks k-steps of WV voxels for the
+// first ntg (uniform, <= NT) of NT X images that share one dY image.  load_rows(ks, rd, rx) fills
+// this thread's 16-B chunks (voxel row tid >> 3 of k-step ks, channels 8 (tid & 7) ..) of dY and of
+// the X images; they arrive zeroed, so a row or tap without a voxel is left alone.  COT x CIT = the
+// workgroup's (co, ci) tile, 64 or 32 each (a 32-channel level stages half rows).  The next k-step's
+// rows are loaded into registers while this one's MFMAs run.
+template <int COT, int CIT, int NT, class LoadF>
+PCS_DEV void wgrad_tile(LoadF load_rows, int nks, int ntg, f32x4 (&acc_out)[NT][COT / 32][CIT / 32]) {
+  __shared__ __attribute__((aligned(16))) char lds[2][(1 + NT) * WIMG];   // per buffer: dY | X per image
+  constexpr int NI = COT / 32, NJ = CIT / 32;   // 16-channel MFMA tiles per wave (co, ci)
+  // the loop accumulates in locals and hands them over once: accumulating through the reference
+  // left the compiler with two copies of every accumulator (30 more VGPRs, a wave less per SIMD)
+  f32x4 acc[NT][NI][NJ];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int wr = wid >> 1, wc = wid & 1;
+  const int sv = tid >> 3, q8 = tid & 7;   // staging: voxel row sv, 16-B chunk q8
+#pragma unroll
+  for (int a = 0; a < NT; ++a)
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc[a][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  u32x4 rd, rx[NT];
+  auto load = [&](int ks) {
+    rd = mk_u32x4(0, 0, 0, 0);
+#pragma unroll
+    for (int a = 0; a < NT; ++a) rx[a] = mk_u32x4(0, 0, 0, 0);
+    load_rows(ks, rd, rx);
+  };
+  auto stage = [&](int buf) {
+    *reinterpret_cast<u32x4 *>(lds[buf] + woff(sv, q8 * 16)) = rd;
+#pragma unroll
+    for (int a = 0; a < NT; ++a)
+      if (a < ntg) *reinterpret_cast<u32x4 *>(lds[buf] + (1 + a) * WIMG + woff(sv, q8 * 16)) = rx[a];
+  };
+  if (nks > 0) {
+    load(0);
+    stage(0);
+  }
+  __syncthreads();
+  for (int ks = 0; ks < nks; ++ks) {
+    const int buf = ks & 1;
+    if (ks + 1 < nks) load(ks + 1);
+    bf16x8 fd[NI];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) fd[i] = wfrag(lds[buf], wr * (COT / 2) + i * 16, lane);
+#pragma unroll
+    for (int a = 0; a < NT; ++a) {
+      if (a < ntg) {   // uniform
+        bf16x8 fx[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) fx[j] = wfrag(lds[buf] + (1 + a) * WIMG, wc * (CIT / 2) + j * 16, lane);
+        // lane: dW rows co = 4 lg + v of tile i, column ci = lr of tile j
+#pragma unroll
+        for (int i = 0; i < NI; ++i)
+#pragma unroll
+          for (int j = 0; j < NJ; ++j)
+            acc[a][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd[i], fx[j], acc[a][i][j], 0, 0, 0);
+      }
+    }
+    if (ks + 1 < nks) stage(buf ^ 1);   // buf ^ 1 was last read before the previous barrier
+    __syncthreads();
+  }
+#pragma unroll
+  for (int a = 0; a < NT; ++a)
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) acc_out[a][i][j] = acc[a][i][j];
+}
+
+// one image's accumulators of wgrad_tile, the (co0, ci0) tile of tap t -> out[co][t][ci]
+template <int COT, int CIT>
+PCS_DEV void store_wgrad_tile(const f32x4 (&acc)[COT / 32][CIT / 32], float *__restrict__ out, int co0, int taps, int t,
+                              int ci0, int Cin) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < COT / 32; ++i)
+#pragma unroll
+    for (int j = 0; j < CIT / 32; ++j) {
+      const int ci = ci0 + wc * (CIT / 2) + j * 16 + lr;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int co = co0 + wr * (COT / 2) + i * 16 + 4 * lg + v;
+        out[((int64_t)co * taps + t) * Cin + ci] = acc[i][j][v];
+      }
+    }
+}
+
 template <int COT, int CIT>
 __global__ __launch_bounds__(THREADS) void conv3d_wgrad_kernel(pcs_conv3d_geom g, const bf16_t *__restrict__ X,
                                                                const bf16_t *__restrict__ dY, float *__restrict__ ws,
                                                                int64_t M, int64_t vps) {
-  __shared__ __attribute__((aligned(16))) char lds[2][(1 + TG) * WIMG];   // per buffer: dY | X per dx tap
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
-  constexpr int NI = COT / 32, NJ = CIT / 32;   // 16-channel MFMA tiles per wave (co, ci)
   const int nco = g.Cout / COT;
   const int co0 = (blockIdx.x % nco) * COT, ci0 = (blockIdx.x / nco) * CIT;
   const int split = blockIdx.z;
@@ -443,92 +579,34 @@ __global__ __launch_bounds__(THREADS) void conv3d_wgrad_kernel(pcs_conv3d_geom g
     vs = ((Mv + gridDim.z - 1) / gridDim.z + WV - 1) / WV * WV;
   }
   const int64_t lo = (int64_t)split * vs, hi = pcs_min64(lo + vs, Mv);
-  const int sv = tid >> 3, q8 = tid & 7;   // staging: voxel row sv, 16-B chunk q8 (channels 8 q8 ..)
-
-  f32x4 acc[TG][NI][NJ];
-#pragma unroll
-  for (int a = 0; a < TG; ++a)
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) acc[a][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // the next k-step's rows are loaded into registers while this one's MFMAs run
-  u32x4 rd, rx[TG];
-  auto load = [&](int64_t v0) {
-    const int64_t u = v0 + sv;
-    rd = mk_u32x4(0, 0, 0, 0);
-#pragma unroll
-    for (int a = 0; a < TG; ++a) rx[a] = mk_u32x4(0, 0, 0, 0);
-    if (u < hi) {
-      int b, z, y, x;
-      int64_t uo = u;
-      if (cm) {
-        decode_class(pc, u, b, z, y, x);
-        uo = (((int64_t)b * g.Do + z) * g.Ho + y) * g.Wo + x;
-      } else {
-        decode(g, u, b, z, y, x);
-      }
-      if (q8 < COT / 8) rd = *reinterpret_cast<const u32x4 *>(dY + uo * g.Cout + co0 + q8 * 8);
-#pragma unroll
-      for (int a = 0; a < TG; ++a) {
-        if (a < ntg) {
-          const int64_t iv = in_voxel(g, b, z, y, x, dz, dy, dx0 + a);
-          if (iv >= 0 && q8 < CIT / 8) rx[a] = *reinterpret_cast<const u32x4 *>(X + iv * g.Cin + ci0 + q8 * 8);
-        }
-      }
+  const int sv = threadIdx.x >> 3, q8 = threadIdx.x & 7;
+  auto load_rows = [&](int ks, u32x4 &rd, u32x4 (&rx)[TG]) {
+    const int64_t u = lo + (int64_t)ks * WV + sv;
+    if (u >= hi) return;
+    int b, z, y, x;
+    int64_t uo = u;
+    if (cm) {
+      decode_class(pc, u, b, z, y, x);
+      uo = (((int64_t)b * g.Do + z) * g.Ho + y) * g.Wo + x;
+    } else {
+      decode(g, u, b, z, y, x);
     }
-  };
-  auto stage = [&](int buf) {
-    *reinterpret_cast<u32x4 *>(lds[buf] + woff(sv, q8 * 16)) = rd;
-#pragma unroll
-    for (int a = 0; a < TG; ++a)
-      if (a < ntg) *reinterpret_cast<u32x4 *>(lds[buf] + (1 + a) * WIMG + woff(sv, q8 * 16)) = rx[a];
-  };
-  const int nks = (int)((hi - lo + WV - 1) / WV);   // uniform; 0 for an empty slice
-  if (nks > 0) {
-    load(lo);
-    stage(0);
-  }
-  __syncthreads();
-  for (int ks = 0; ks < nks; ++ks) {
-    const int buf = ks & 1;
-    if (ks + 1 < nks) load(lo + (int64_t)(ks + 1) * WV);
-    bf16x8 fd[NI];
-#pragma unroll
-    for (int i = 0; i < NI; ++i) fd[i] = wfrag(lds[buf], wr * (COT / 2) + i * 16, lane);
+    if (q8 < COT / 8) rd = *reinterpret_cast<const u32x4 *>(dY + uo * g.Cout + co0 + q8 * 8);
 #pragma unroll
     for (int a = 0; a < TG; ++a) {
-      if (a < ntg) {   // uniform
-        bf16x8 fx[NJ];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) fx[j] = wfrag(lds[buf] + (1 + a) * WIMG, wc * (CIT / 2) + j * 16, lane);
-        // lane: dW rows co = 4 lg + v of tile i, column ci = lr of tile j
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            acc[a][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd[i], fx[j], acc[a][i][j], 0, 0, 0);
+      if (a < ntg) {
+        const int64_t iv = in_voxel(g, b, z, y, x, dz, dy, dx0 + a);
+        if (iv >= 0 && q8 < CIT / 8) rx[a] = *reinterpret_cast<const u32x4 *>(X + iv * g.Cin + ci0 + q8 * 8);
       }
     }
-    if (ks + 1 < nks) stage(buf ^ 1);   // buf ^ 1 was last read before the previous barrier
-    __syncthreads();
-  }
+  };
+  f32x4 acc[TG][COT / 32][CIT / 32];
+  wgrad_tile<COT, CIT, TG>(load_rows, (int)((hi - lo + WV - 1) / WV), ntg, acc);   // (uniform; 0 k-steps for an empty slice)
   float *out = ws + (int64_t)split * g.Cout * taps * g.Cin;
 #pragma unroll
   for (int a = 0; a < TG; ++a) {
     if (a >= ntg) continue;
-    const int t = (dz * k + dy) * k + dx0 + a;
-#pragma unroll
-    for (int i = 0; i < NI; ++i)
-#pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const int ci = ci0 + wc * (CIT / 2) + j * 16 + lr;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int co = co0 + wr * (COT / 2) + i * 16 + 4 * lg + v;
-          out[((int64_t)co * taps + t) * g.Cin + ci] = acc[a][i][j][v];
-        }
-      }
+    store_wgrad_tile<COT, CIT>(acc[a], out, co0, taps, (dz * k + dy) * k + dx0 + a, ci0, g.Cin);
   }
 }
 
@@ -706,22 +784,11 @@ __global__ __launch_bounds__(THREADS) void sparse_conv_kernel(const int32_t *__r
                                                               const bf16_t *__restrict__ W, int Cout,
                                                               const float *__restrict__ bias, void *__restrict__ Y,
                                                               int flip) {
-  constexpr int RB = KST * 2;
-  constexpr int CPR = KST / 8;
-  constexpr int RPP = THREADS / CPR;
-  constexpr int HA = BMT / RPP, HB = BN / RPP;
-  constexpr int TI = BMT / 32;
-  constexpr int KK = KST / 32;
-  __shared__ __attribute__((aligned(16))) char lds[2][(BMT + BN) * RB];
   __shared__ uint32_t tmask;
   __shared__ int tlist[32];
   __shared__ int ntl;
-  auto swzf = [](int row, int slot) { return KST == 32 ? cswz(row, slot) : (slot ^ ((row >> 1) & 7)); };
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
+  const int tid = threadIdx.x;
   const int64_t m0 = (int64_t)blockIdx.x * BMT;
-  const int n0 = blockIdx.y * BN;
-  const int srow = tid / CPR, q = tid % CPR;
 
   // the taps this tile meets
   if (tid == 0) tmask = 0u;
@@ -741,94 +808,11 @@ __global__ __launch_bounds__(THREADS) void sparse_conv_kernel(const int32_t *__r
     ntl = c;
   }
   __syncthreads();
-  const int cps = Cin / KST;
-  const int nks = ntl * cps;
-  const bf16_t *wrow = W + (int64_t)(n0 + srow) * taps * Cin + q * 8;
-  const int64_t wstep = (int64_t)RPP * taps * Cin;
-
-  u32x4 ra[HA], rb[HB];
-  auto load = [&](int ks) {
-    const int j = ks / cps, c0 = (ks - j * cps) * KST;
-    const int t = tlist[j], tw = flip ? taps - 1 - t : t;
-#pragma unroll
-    for (int h = 0; h < HA; ++h) {
-      const int64_t u = m0 + srow + RPP * h;
-      const int iv = u < M ? nbr[u * taps + t] : -1;
-      ra[h] = iv >= 0 ? *reinterpret_cast<const u32x4 *>(X + (int64_t)iv * Cin + c0 + q * 8) : mk_u32x4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int h = 0; h < HB; ++h) rb[h] = *reinterpret_cast<const u32x4 *>(wrow + h * wstep + (int64_t)tw * Cin + c0);
-  };
-  auto stage = [&](int buf) {
-    char *tA = lds[buf], *tB = lds[buf] + BMT * RB;
-#pragma unroll
-    for (int h = 0; h < HA; ++h) {
-      const int r = srow + RPP * h;
-      *reinterpret_cast<u32x4 *>(tA + r * RB + swzf(r, q) * 16) = ra[h];
-    }
-#pragma unroll
-    for (int h = 0; h < HB; ++h) {
-      const int r = srow + RPP * h;
-      *reinterpret_cast<u32x4 *>(tB + r * RB + swzf(r, q) * 16) = rb[h];
-    }
-  };
-
-  f32x4 acc[TI][2];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (nks > 0) {
-    load(0);
-    stage(0);
-  }
-  __syncthreads();
-  for (int ks = 0; ks < nks; ++ks) {
-    const int buf = ks & 1;
-    if (ks + 1 < nks) load(ks + 1);
-    const char *tA = lds[buf], *tB = lds[buf] + BMT * RB;
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-      bf16x8 af[TI], bw[2];
-#pragma unroll
-      for (int i = 0; i < TI; ++i) {
-        const int r = wr * (BMT / 2) + i * 16 + lr;
-        af[i] = *reinterpret_cast<const bf16x8 *>(tA + r * RB + swzf(r, kk * 4 + lg) * 16);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int r = wc * 32 + j * 16 + lr;
-        bw[j] = *reinterpret_cast<const bf16x8 *>(tB + r * RB + swzf(r, kk * 4 + lg) * 16);
-      }
-#pragma unroll
-      for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[j], af[i], acc[i][j], 0, 0, 0);
-    }
-    if (ks + 1 < nks) stage(buf ^ 1);
-    __syncthreads();
-  }
-
-#pragma unroll
-  for (int i = 0; i < TI; ++i) {
-    const int64_t uo = m0 + wr * (BMT / 2) + i * 16 + lr;
-    if (uo >= M) continue;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int co = n0 + wc * 32 + j * 16 + 4 * lg;
-      float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-      if (bias) {
-        const float4 bb = *reinterpret_cast<const float4 *>(bias + co);
-        v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-      }
-      if constexpr (OUT_BF16) {
-        *reinterpret_cast<uint2 *>(reinterpret_cast<bf16_t *>(Y) + uo * Cout + co) =
-            make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
-      } else {
-        *reinterpret_cast<float4 *>(reinterpret_cast<float *>(Y) + uo * Cout + co) = make_float4(v[0], v[1], v[2], v[3]);
-      }
-    }
-  }
+  auto in_row = [&](int, int r, int j) { return m0 + r < M ? nbr[(m0 + r) * taps + tlist[j]] : -1; };
+  auto wtap = [&](int j) { return flip ? taps - 1 - tlist[j] : tlist[j]; };
+  f32x4 acc[BMT / 32][2];
+  gather_gemm_tile<BMT, KST, BN>(X, Cin, W, taps, blockIdx.y * BN, ntl, in_row, wtap, acc);
+  store_tile<BMT, BN, OUT_BF16>(acc, [&](int r) { return m0 + r < M ? m0 + r : -1; }, blockIdx.y * BN, Cout, bias, Y);
 }
 
 // weight gradient of the sparse convolution: dW[co][t][ci] = sum_m dY[m][co] X[nbr[m][t]][ci];
@@ -838,89 +822,30 @@ __global__ __launch_bounds__(THREADS) void sparse_wgrad_kernel(const int32_t *__
                                                                const bf16_t *__restrict__ X, int Cin,
                                                                const bf16_t *__restrict__ dY, int Cout,
                                                                float *__restrict__ ws, int64_t vps) {
-  __shared__ __attribute__((aligned(16))) char lds[2][(1 + TG) * WIMG];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
   const int nco = Cout / 64;
   const int co0 = (blockIdx.x % nco) * 64, ci0 = (blockIdx.x / nco) * 64;
   const int t0 = blockIdx.y * TG, ntg = min(TG, taps - t0);
   const int64_t lo = (int64_t)blockIdx.z * vps, hi = pcs_min64(lo + vps, M);
-  const int sv = tid >> 3, q8 = tid & 7;
-
-  f32x4 acc[TG][2][2];
-#pragma unroll
-  for (int a = 0; a < TG; ++a)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[a][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  u32x4 rd, rx[TG];
-  auto load = [&](int64_t v0) {
-    const int64_t u = v0 + sv;
-    rd = mk_u32x4(0, 0, 0, 0);
-#pragma unroll
-    for (int a = 0; a < TG; ++a) rx[a] = mk_u32x4(0, 0, 0, 0);
-    if (u < hi) {
-      rd = *reinterpret_cast<const u32x4 *>(dY + u * Cout + co0 + q8 * 8);
-#pragma unroll
-      for (int a = 0; a < TG; ++a) {
-        if (a < ntg) {
-          const int iv = nbr[u * taps + t0 + a];
-          if (iv >= 0) rx[a] = *reinterpret_cast<const u32x4 *>(X + (int64_t)iv * Cin + ci0 + q8 * 8);
-        }
-      }
-    }
-  };
-  auto stage = [&](int buf) {
-    *reinterpret_cast<u32x4 *>(lds[buf] + woff(sv, q8 * 16)) = rd;
-#pragma unroll
-    for (int a = 0; a < TG; ++a)
-      if (a < ntg) *reinterpret_cast<u32x4 *>(lds[buf] + (1 + a) * WIMG + woff(sv, q8 * 16)) = rx[a];
-  };
-  const int nks = (int)((hi - lo + WV - 1) / WV);
-  if (nks > 0) {
-    load(lo);
-    stage(0);
-  }
-  __syncthreads();
-  for (int ks = 0; ks < nks; ++ks) {
-    const int buf = ks & 1;
-    if (ks + 1 < nks) load(lo + (int64_t)(ks + 1) * WV);
-    bf16x8 fd[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) fd[i] = wfrag(lds[buf], wr * 32 + i * 16, lane);
+  const int sv = threadIdx.x >> 3, q8 = threadIdx.x & 7;
+  auto load_rows = [&](int ks, u32x4 &rd, u32x4 (&rx)[TG]) {
+    const int64_t u = lo + (int64_t)ks * WV + sv;
+    if (u >= hi) return;
+    rd = *reinterpret_cast<const u32x4 *>(dY + u * Cout + co0 + q8 * 8);
 #pragma unroll
     for (int a = 0; a < TG; ++a) {
       if (a < ntg) {
-        bf16x8 fx[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) fx[j] = wfrag(lds[buf] + (1 + a) * WIMG, wc * 32 + j * 16, lane);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[a][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd[i], fx[j], acc[a][i][j], 0, 0, 0);
+        const int iv = nbr[u * taps + t0 + a];
+        if (iv >= 0) rx[a] = *reinterpret_cast<const u32x4 *>(X + (int64_t)iv * Cin + ci0 + q8 * 8);
       }
     }
-    if (ks + 1 < nks) stage(buf ^ 1);
-    __syncthreads();
-  }
+  };
+  f32x4 acc[TG][2][2];
+  wgrad_tile<64, 64, TG>(load_rows, (int)((hi - lo + WV - 1) / WV), ntg, acc);
   float *out = ws + (int64_t)blockIdx.z * Cout * taps * Cin;
 #pragma unroll
   for (int a = 0; a < TG; ++a) {
     if (a >= ntg) continue;
-    const int t = t0 + a;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int ci = ci0 + wc * 32 + j * 16 + lr;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          const int co = co0 + wr * 32 + i * 16 + 4 * lg + v;
-          out[((int64_t)co * taps + t) * Cin + ci] = acc[a][i][j][v];
-        }
-      }
+    store_wgrad_tile<64, 64>(acc[a], out, co0, taps, t0 + a, ci0, Cin);
   }
 }
 
@@ -1099,90 +1024,27 @@ __global__ __launch_bounds__(256) void pairs_build_kernel(const int32_t *__restr
   for (int i = tid; i < nr * taps; i += 256) ppos[r0 * taps + i] = rb[i];
 }
 
-// The tile loop of the two pair GEMMs below: acc = W[tw(t)] X[pair_in[p]] (fp32) for the 64 pairs
-// [p0, pend) of tile blockIdx.x, which belongs to tap t, and the 64 output channels from
-// blockIdx.y * BN; lane (lr, lg) of wave (wr, wc) holds pairs p0 + wr * 32 + i * 16 + lr, channels
-// n0 + wc * 32 + j * 16 + 4 * lg .. + 3 in acc[i][j].
+// The tile of the two pair GEMMs below: acc = W[wt] X[pair_in[p]] (gather_gemm_tile on one tap)
+// for the 64 pairs [p0, pend) of tile blockIdx.x, which belongs to tap t (wt = taps - 1 - t under
+// flip), and the 64 output channels from blockIdx.y * BN.
 template <int KST>
 PCS_DEV void pair_tile(const PairTaps &pt, const int32_t *__restrict__ pin, const bf16_t *__restrict__ X, int Cin,
                        const bf16_t *__restrict__ W, int flip, f32x4 (&acc)[2][2], int64_t &p0, int64_t &pend) {
-  constexpr int BMT = 64, RB = KST * 2, CPR = KST / 8, RPP = THREADS / CPR;
-  constexpr int HA = BMT / RPP, HB = BN / RPP, KK = KST / 32;
-  __shared__ __attribute__((aligned(16))) char lds[2][(BMT + BN) * RB];
-  auto swzf = [](int row, int slot) { return KST == 32 ? cswz(row, slot) : (slot ^ ((row >> 1) & 7)); };
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
+  constexpr int RPP = THREADS / (KST / 8), HA = 64 / RPP;   // gather_gemm_tile's staging passes
   const int taps = pt.taps, tile = blockIdx.x;
   int t = 0;
   while (t + 1 < taps && pt.tile_off[t + 1] <= tile) ++t;
-  const int tw = flip ? taps - 1 - t : t;
-  p0 = pt.tap_off[t] + (int64_t)(tile - pt.tile_off[t]) * BMT;
+  p0 = pt.tap_off[t] + (int64_t)(tile - pt.tile_off[t]) * 64;
   pend = pt.tap_off[t + 1];
-  const int n0 = blockIdx.y * BN;
-  const int srow = tid / CPR, q = tid % CPR;
   int iv[HA];
 #pragma unroll
   for (int h = 0; h < HA; ++h) {
-    const int64_t p = p0 + srow + RPP * h;
+    const int64_t p = p0 + threadIdx.x / (KST / 8) + RPP * h;
     iv[h] = p < pend ? pin[p] : -1;
   }
-  const bf16_t *wrow = W + ((int64_t)(n0 + srow) * taps + tw) * Cin + q * 8;
-  const int64_t wstep = (int64_t)RPP * taps * Cin;
-  const int nks = Cin / KST;
-  u32x4 ra[HA], rb[HB];
-  auto load = [&](int ks) {
-    const int c0 = ks * KST;
-#pragma unroll
-    for (int h = 0; h < HA; ++h)
-      ra[h] = iv[h] >= 0 ? *reinterpret_cast<const u32x4 *>(X + (int64_t)iv[h] * Cin + c0 + q * 8) : mk_u32x4(0, 0, 0, 0);
-#pragma unroll
-    for (int h = 0; h < HB; ++h) rb[h] = *reinterpret_cast<const u32x4 *>(wrow + h * wstep + c0);
-  };
-  auto stage = [&](int buf) {
-    char *tA = lds[buf], *tB = lds[buf] + BMT * RB;
-#pragma unroll
-    for (int h = 0; h < HA; ++h) {
-      const int r = srow + RPP * h;
-      *reinterpret_cast<u32x4 *>(tA + r * RB + swzf(r, q) * 16) = ra[h];
-    }
-#pragma unroll
-    for (int h = 0; h < HB; ++h) {
-      const int r = srow + RPP * h;
-      *reinterpret_cast<u32x4 *>(tB + r * RB + swzf(r, q) * 16) = rb[h];
-    }
-  };
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  load(0);
-  stage(0);
-  __syncthreads();
-  for (int ks = 0; ks < nks; ++ks) {
-    const int buf = ks & 1;
-    if (ks + 1 < nks) load(ks + 1);
-    const char *tA = lds[buf], *tB = lds[buf] + BMT * RB;
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-      bf16x8 af[2], bw[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int r = wr * 32 + i * 16 + lr;
-        af[i] = *reinterpret_cast<const bf16x8 *>(tA + r * RB + swzf(r, kk * 4 + lg) * 16);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int r = wc * 32 + j * 16 + lr;
-        bw[j] = *reinterpret_cast<const bf16x8 *>(tB + r * RB + swzf(r, kk * 4 + lg) * 16);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bw[j], af[i], acc[i][j], 0, 0, 0);
-    }
-    if (ks + 1 < nks) stage(buf ^ 1);
-    __syncthreads();
-  }
+  const int wt = flip ? taps - 1 - t : t;
+  gather_gemm_tile<64, KST, BN>(X, Cin, W, taps, blockIdx.y * BN, 1, [&](int h, int, int) { return iv[h]; },
+                                [&](int) { return wt; }, acc);
 }
 
 // Z[p][n0 ..] = W[tw(t)] X[pair_in[p]] for the 64 pairs of one tile of tap t (fp32 products).
@@ -1244,7 +1106,7 @@ __global__ __launch_bounds__(256) void pair_reduce_kernel(const int32_t *__restr
 // Y[pair_out[p]] = b + W[t] X[pair_in[p]] for the 64 pairs of one tile of tap t, where every output
 // row has exactly one pair (the up-convolution of a k = 2, s = 2 level, and the down-convolution's
 // input gradient: a fine voxel has one parent and sits at one tap of it).  pair_gemm_kernel's
-// tile loop with sparse_conv_kernel's epilogue scattered through pair_out: no Z, no reduce pass.
+// tile with the forward epilogue scattered through pair_out: no Z, no reduce pass.
 template <int KST, bool OUT_BF16>
 __global__ __launch_bounds__(THREADS) void pair_rows_kernel(PairTaps pt, const int32_t *__restrict__ pin,
                                                             const int32_t *__restrict__ pout,
@@ -1252,48 +1114,26 @@ __global__ __launch_bounds__(THREADS) void pair_rows_kernel(PairTaps pt, const i
                                                             const bf16_t *__restrict__ W, int Cout,
                                                             const float *__restrict__ bias, int64_t M,
                                                             void *__restrict__ Y) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
-  const int n0 = blockIdx.y * BN;
   f32x4 acc[2][2];
   int64_t p0, pend;
   pair_tile<KST>(pt, pin, X, Cin, W, 0, acc, p0, pend);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int64_t p = p0 + wr * 32 + i * 16 + lr;
-    if (p >= pend) continue;
-    const int64_t uo = pout[p];
-    if (uo < 0 || uo >= M) continue;   // (not a row of Y: a list that breaks the precondition)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int co = n0 + wc * 32 + j * 16 + 4 * lg;
-      float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-      if (bias) {
-        const float4 bb = *reinterpret_cast<const float4 *>(bias + co);
-        v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
-      }
-      if constexpr (OUT_BF16) {
-        *reinterpret_cast<uint2 *>(reinterpret_cast<bf16_t *>(Y) + uo * Cout + co) =
-            make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
-      } else {
-        *reinterpret_cast<float4 *>(reinterpret_cast<float *>(Y) + uo * Cout + co) = make_float4(v[0], v[1], v[2], v[3]);
-      }
-    }
-  }
+  auto out_row = [&](int r) -> int64_t {
+    if (p0 + r >= pend) return -1;
+    const int64_t uo = pout[p0 + r];
+    return uo < M ? uo : -1;   // (negative or >= M: not a row of Y, a list that breaks the precondition)
+  };
+  store_tile<64, BN, OUT_BF16>(acc, out_row, blockIdx.y * BN, Cout, bias, Y);
 }
 
 // dW_t partial of one pair slice g of tap t: sum over its pairs of dY[pair_out] (x) X[pair_in] into
-// ws[g][co][ci] (the k-over-rows MFMA operands of conv3d_wgrad_kernel, gathered through the pair
-// list).  Slices are a fixed number of pairs, so a tap's slice count follows its pair count (the
-// centre tap has every row) and every workgroup has about the same work.
+// ws[g][co][ci] (wgrad_tile with one X image, gathered through the pair list).  Slices are a fixed
+// number of pairs, so a tap's slice count follows its pair count (the centre tap has every row)
+// and every workgroup has about the same work.
 __global__ __launch_bounds__(THREADS) void pair_wgrad_kernel(PairTaps pt, const int32_t *__restrict__ pin,
                                                              const int32_t *__restrict__ pout,
                                                              const bf16_t *__restrict__ X, int Cin,
                                                              const bf16_t *__restrict__ dY, int Cout,
                                                              float *__restrict__ ws) {
-  __shared__ __attribute__((aligned(16))) char lds[2][2 * WIMG];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
   const int nco = Cout / 64, taps = pt.taps;
   const int co0 = (blockIdx.x % nco) * 64, ci0 = (blockIdx.x / nco) * 64;
   const int g = blockIdx.y;
@@ -1301,59 +1141,16 @@ __global__ __launch_bounds__(THREADS) void pair_wgrad_kernel(PairTaps pt, const 
   while (t + 1 < taps && pt.slice_off[t + 1] <= g) ++t;
   const int64_t cnt = pt.tap_off[t + 1] - pt.tap_off[t], s0 = (int64_t)(g - pt.slice_off[t]) * pt.slice_len;
   const int64_t lo = pt.tap_off[t] + pcs_min64(s0, cnt), hi = pt.tap_off[t] + pcs_min64(s0 + pt.slice_len, cnt);
-  const int sv = tid >> 3, q8 = tid & 7;
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  u32x4 rd, rx;
-  auto load = [&](int64_t p0) {
-    const int64_t p = p0 + sv;
-    rd = mk_u32x4(0, 0, 0, 0);
-    rx = mk_u32x4(0, 0, 0, 0);
-    if (p < hi) {
-      rd = *reinterpret_cast<const u32x4 *>(dY + (int64_t)pout[p] * Cout + co0 + q8 * 8);
-      rx = *reinterpret_cast<const u32x4 *>(X + (int64_t)pin[p] * Cin + ci0 + q8 * 8);
-    }
+  const int sv = threadIdx.x >> 3, q8 = threadIdx.x & 7;
+  auto load_rows = [&](int ks, u32x4 &rd, u32x4 (&rx)[1]) {
+    const int64_t p = lo + (int64_t)ks * WV + sv;
+    if (p >= hi) return;
+    rd = *reinterpret_cast<const u32x4 *>(dY + (int64_t)pout[p] * Cout + co0 + q8 * 8);
+    rx[0] = *reinterpret_cast<const u32x4 *>(X + (int64_t)pin[p] * Cin + ci0 + q8 * 8);
   };
-  auto stage = [&](int buf) {
-    *reinterpret_cast<u32x4 *>(lds[buf] + woff(sv, q8 * 16)) = rd;
-    *reinterpret_cast<u32x4 *>(lds[buf] + WIMG + woff(sv, q8 * 16)) = rx;
-  };
-  const int nks = (int)((hi - lo + WV - 1) / WV);   // uniform; 0 for an empty slice
-  if (nks > 0) {
-    load(lo);
-    stage(0);
-  }
-  __syncthreads();
-  for (int ks = 0; ks < nks; ++ks) {
-    const int buf = ks & 1;
-    if (ks + 1 < nks) load(lo + (int64_t)(ks + 1) * WV);
-    bf16x8 fd[2], fx[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) fd[i] = wfrag(lds[buf], wr * 32 + i * 16, lane);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) fx[j] = wfrag(lds[buf] + WIMG, wc * 32 + j * 16, lane);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fd[i], fx[j], acc[i][j], 0, 0, 0);
-    if (ks + 1 < nks) stage(buf ^ 1);
-    __syncthreads();
-  }
-  float *out = ws + (int64_t)g * Cout * Cin;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int ci = ci0 + wc * 32 + j * 16 + lr;
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int co = co0 + wr * 32 + i * 16 + 4 * lg + v;
-        out[(int64_t)co * Cin + ci] = acc[i][j][v];
-      }
-    }
+  f32x4 acc[1][2][2];
+  wgrad_tile<64, 64, 1>(load_rows, (int)((hi - lo + WV - 1) / WV), 1, acc);   // (uniform; 0 k-steps for an empty slice)
+  store_wgrad_tile<64, 64>(acc[0], ws + (int64_t)g * Cout * Cin, co0, 1, 0, ci0, Cin);
 }
 
 // dW[co][t][ci] = sum over tap t's slices in order of ws[g][co][ci]
@@ -1370,6 +1167,29 @@ __global__ __launch_bounds__(256) void pair_wgrad_reduce_kernel(PairTaps pt, con
   dW[i] = s;
 }
 
+// LAUNCH(KST, OUT_BF16) of a forward gather kernel: 64-channel k-steps where Cin allows, Y's dtype
+#define PCS_KST_OB(K64, OB, LAUNCH)                                     \
+  do {                                                                  \
+    if (K64) { if (OB) LAUNCH(64, true); else LAUNCH(64, false); }      \
+    else { if (OB) LAUNCH(32, true); else LAUNCH(32, false); }          \
+  } while (0)
+
+// db = column sums of dY [M, Cout] through the sp slice partials wsb (vps rows per slice), the tail
+// of every weight-gradient entry point (who: its name, for the error text)
+int bias_grad(const void *dY, int Cout, int64_t M, int64_t sp, int64_t vps, float *wsb, float *db, hipStream_t s,
+              const char *who) {
+  hipError_t e = hipSuccess;
+  if (M > 0)
+    hipLaunchKernelGGL(conv3d_bgrad_kernel, dim3((unsigned)((Cout + 63) / 64), (unsigned)sp), dim3(THREADS), 0, s,
+                       static_cast<const bf16_t *>(dY), Cout, M, vps, wsb);
+  else
+    e = hipMemsetAsync(wsb, 0, sp * Cout * 4, s);
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e != hipSuccess) return pcs_set_error(e, who);
+  hipLaunchKernelGGL(conv3d_reduce_kernel, dim3((unsigned)((Cout + 255) / 256)), dim3(256), 0, s, wsb, sp, (int64_t)Cout, db);
+  e = hipGetLastError();
+  return e != hipSuccess ? pcs_set_error(e, who) : 0;
+}
 
 }  // namespace
 
@@ -1409,20 +1229,15 @@ extern "C" int pcs_conv3d(const pcs_conv3d_geom *g, const void *X, const void *W
   if (tiles <= 0 || tiles > 0x7fffffff) return pcs_set_einval("pcs_conv3d", "grid too large");
   const dim3 grid((unsigned)tiles, (unsigned)ncb);
   const bf16_t *Xb = static_cast<const bf16_t *>(X), *Wb = static_cast<const bf16_t *>(W);
-  const bool k64 = cs == 64;
 #define PCS_C3(BMT, KST, OB, NT) \
   hipLaunchKernelGGL((conv3d_kernel<BMT, KST, OB, NT>), grid, dim3(THREADS), 0, s, *g, Xb, Wb, bias, Y, M)
-#define PCS_C3K(BMT, OB)                                          \
-  do {                                                            \
-    if (nt == 64) { if (k64) PCS_C3(BMT, 64, OB, 64); else PCS_C3(BMT, 32, OB, 64); } \
-    else { if (k64) PCS_C3(BMT, 64, OB, 32); else PCS_C3(BMT, 32, OB, 32); }          \
+#define PCS_C3T(KST, OB)                                                                  \
+  do {                                                                                    \
+    if (bmt == 128) { if (nt == 64) PCS_C3(128, KST, OB, 64); else PCS_C3(128, KST, OB, 32); } \
+    else { if (nt == 64) PCS_C3(64, KST, OB, 64); else PCS_C3(64, KST, OB, 32); }         \
   } while (0)
-  if (bmt == 128) {
-    if (ydtype == PCS_BF16) PCS_C3K(128, true); else PCS_C3K(128, false);
-  } else {
-    if (ydtype == PCS_BF16) PCS_C3K(64, true); else PCS_C3K(64, false);
-  }
-#undef PCS_C3K
+  PCS_KST_OB(cs == 64, ydtype == PCS_BF16, PCS_C3T);
+#undef PCS_C3T
 #undef PCS_C3
   PCS_CHECK_LAUNCH();
   return 0;
@@ -1469,15 +1284,7 @@ extern "C" int pcs_conv3d_wgrad(const pcs_conv3d_geom *g, const void *X, const v
   PCS_CHECK_LAUNCH();
   hipLaunchKernelGGL(conv3d_reduce_kernel, dim3((unsigned)((wlen + 255) / 256)), dim3(256), 0, s, ws, sp, wlen, dW);
   PCS_CHECK_LAUNCH();
-  if (db) {
-    hipLaunchKernelGGL(conv3d_bgrad_kernel, dim3((unsigned)((g->Cout + 63) / 64), (unsigned)sp), dim3(THREADS), 0, s,
-                       static_cast<const bf16_t *>(dY), g->Cout, M, vps, wsb);
-    PCS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(conv3d_reduce_kernel, dim3((unsigned)((g->Cout + 255) / 256)), dim3(256), 0, s, wsb, sp,
-                       (int64_t)g->Cout, db);
-    PCS_CHECK_LAUNCH();
-  }
-  return 0;
+  return db ? bias_grad(dY, g->Cout, M, sp, vps, wsb, db, s, __func__) : 0;
 }
 
 extern "C" int pcs_conv3d_weight_t(const void *W, int32_t Cout, int32_t taps, int32_t Cin, void *Wt, pcs_stream_t stream) {
@@ -1511,11 +1318,7 @@ extern "C" int pcs_sparse_conv(const int32_t *nbr, int64_t M, int32_t taps, cons
 #define PCS_SC(KST, OB) \
   hipLaunchKernelGGL((sparse_conv_kernel<64, KST, OB>), grid, dim3(THREADS), 0, s, nbr, M, (int)taps, Xb, (int)Cin, Wb, \
                      (int)Cout, bias, Y, (int)flip)
-  if (Cin % 64 == 0) {
-    if (ydtype == PCS_BF16) PCS_SC(64, true); else PCS_SC(64, false);
-  } else {
-    if (ydtype == PCS_BF16) PCS_SC(32, true); else PCS_SC(32, false);
-  }
+  PCS_KST_OB(Cin % 64 == 0, ydtype == PCS_BF16, PCS_SC);
 #undef PCS_SC
   PCS_CHECK_LAUNCH();
   return 0;
@@ -1551,20 +1354,7 @@ extern "C" int pcs_sparse_conv_wgrad(const int32_t *nbr, int64_t M, int32_t taps
   PCS_CHECK_LAUNCH();
   hipLaunchKernelGGL(conv3d_reduce_kernel, dim3((unsigned)((wlen + 255) / 256)), dim3(256), 0, s, ws, sp, wlen, dW);
   PCS_CHECK_LAUNCH();
-  if (db) {
-    if (M > 0) {
-      hipLaunchKernelGGL(conv3d_bgrad_kernel, dim3((unsigned)(Cout / 64), (unsigned)sp), dim3(THREADS), 0, s,
-                         static_cast<const bf16_t *>(dY), (int)Cout, M, vps, wsb);
-    } else {
-      const hipError_t e = hipMemsetAsync(wsb, 0, sp * Cout * 4, s);
-      if (e != hipSuccess) return pcs_set_error(e, "pcs_sparse_conv_wgrad");
-    }
-    PCS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(conv3d_reduce_kernel, dim3((unsigned)((Cout + 255) / 256)), dim3(256), 0, s, wsb, sp,
-                       (int64_t)Cout, db);
-    PCS_CHECK_LAUNCH();
-  }
-  return 0;
+  return db ? bias_grad(dY, Cout, M, sp, vps, wsb, db, s, __func__) : 0;
 }
 
 // ---- per-tap pair lists (see pairs_count_kernel)
@@ -1671,11 +1461,7 @@ extern "C" int pcs_sparse_conv_rows(const int32_t *pair_in, const int32_t *pair_
 #define PCS_PR(KST, OB) \
   hipLaunchKernelGGL((pair_rows_kernel<KST, OB>), grid, dim3(THREADS), 0, s, pt, pair_in, pair_out, Xb, (int)Cin, Wb, \
                      (int)Cout, bias, M, Y)
-  if (Cin % 64 == 0) {
-    if (ydtype == PCS_BF16) PCS_PR(64, true); else PCS_PR(64, false);
-  } else {
-    if (ydtype == PCS_BF16) PCS_PR(32, true); else PCS_PR(32, false);
-  }
+  PCS_KST_OB(Cin % 64 == 0, ydtype == PCS_BF16, PCS_PR);
 #undef PCS_PR
   PCS_CHECK_LAUNCH();
   return 0;
@@ -1736,19 +1522,7 @@ extern "C" int pcs_sparse_conv_wgrad_pairs(const int32_t *pair_in, const int32_t
   PCS_CHECK_LAUNCH();
   hipLaunchKernelGGL(pair_wgrad_reduce_kernel, dim3((unsigned)((wlen + 255) / 256)), dim3(256), 0, s, pt, ws, (int)Cin, (int)Cout, dW);
   PCS_CHECK_LAUNCH();
-  if (db) {
-    const int64_t spb = sparse_wgrad_splits(M, 1, 64, Cout);
-    const int64_t vps = ((M + spb - 1) / spb + WV - 1) / WV * WV;
-    if (M > 0) {
-      hipLaunchKernelGGL(conv3d_bgrad_kernel, dim3((unsigned)((Cout + 63) / 64), (unsigned)spb), dim3(THREADS), 0, s,
-                         static_cast<const bf16_t *>(dY), (int)Cout, M, vps, wsb);
-    } else {
-      const hipError_t e = hipMemsetAsync(wsb, 0, spb * Cout * 4, s);
-      if (e != hipSuccess) return pcs_set_error(e, "pcs_sparse_conv_wgrad_pairs");
-    }
-    PCS_CHECK_LAUNCH();
-    hipLaunchKernelGGL(conv3d_reduce_kernel, dim3((unsigned)((Cout + 255) / 256)), dim3(256), 0, s, wsb, spb, (int64_t)Cout, db);
-    PCS_CHECK_LAUNCH();
-  }
-  return 0;
+  if (!db) return 0;
+  const int64_t spb = sparse_wgrad_splits(M, 1, 64, Cout);
+  return bias_grad(dY, Cout, M, spb, ((M + spb - 1) / spb + WV - 1) / WV * WV, wsb, db, s, __func__);
 }

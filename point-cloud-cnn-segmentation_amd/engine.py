@@ -246,9 +246,7 @@ class Engine:
         if key not in self._geo:
             a = L.GemmArgs(num_scenes=B, scene_rows=N, K=K, Ncols=ncols, dtype=dtype,
                            prologue=pro, epilogue=epi, chunks_per_scene=0, flags=self.flags)
-            rpc = L.load().pcs_gemm_geometry(ct.byref(a))
-            if rpc <= 0:
-                raise L.PcsError(L.load().pcs_last_error().decode())
+            rpc = L.workspace("pcs_gemm_geometry", ct.byref(a))
             self._geo[key] = (a.chunks_per_scene, rpc)
         return self._geo[key]
 
@@ -541,10 +539,8 @@ class Engine:
             Wg = P["global_feat.weight"]
             sv.wg_eff = wc["global_feat_fp8"][2] if self.fp8 else self._rounded(Wg.reshape(1024, -1))
             G5 = torch.empty(1024, 1024, dtype=torch.float32, device=dev)
-            nbytes = L.load().pcs_gram_raw_workspace(M, 1024)
-            if nbytes < 0:
-                raise L.PcsError(L.load().pcs_last_error().decode())
-            gws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+            nbytes = L.workspace("pcs_gram_raw_workspace", M, 1024)
+            gws =torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
             if draw_beside_gram:
                 draw_masks(3 * torch.cuda.get_device_properties(dev).multi_processor_count)
             self._launch("wgrad:global_feat", "pcs_gram_raw", L.ptr(a5), M, 1024, self.a5_dt, L.ptr(gws), nbytes,
@@ -678,9 +674,7 @@ class Engine:
                         t2=L.ptr(c2.shift), W1=L.ptr(wc["seg_conv1"][0]), sbias=L.ptr(sbias), Y1=L.ptr(y1),
                         s1=L.ptr(c1.scale), t1=L.ptr(c1.shift), keep1=L.ptr(m1), keep_scale=keep,
                         W2=L.ptr(wc["seg_conv2"][0]), Y2=L.ptr(y2))
-        rpc = L.load().pcs_fwd_seg12_geometry(ct.byref(a))
-        if rpc <= 0:
-            raise L.PcsError(L.load().pcs_last_error().decode())
+        rpc = L.workspace("pcs_fwd_seg12_geometry", ct.byref(a))
         cps = a.chunks_per_scene
         st2 = torch.empty(B * cps, 256, 2, dtype=torch.float32, device=dev)
         a.stats = L.ptr(st2)
@@ -869,9 +863,7 @@ class Engine:
                              flags=self.flags, dZ=L.ptr(dz_s1), alpha=L.ptr(a1),
                              beta=L.ptr(b1), gamma=L.ptr(g1), X=L.ptr(ys["conv2"]), s=L.ptr(p2.scale),
                              t=L.ptr(p2.shift))
-            nbytes = L.load().pcs_dgrad_wgrad_folded_workspace(ct.byref(fa))
-            if nbytes < 0:
-                raise L.PcsError(L.load().pcs_last_error().decode())
+            nbytes = L.workspace("pcs_dgrad_wgrad_folded_workspace", ct.byref(fa))
             ws1 = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
             fa.partial = ws1.data_ptr()
             self._launch("dgrad+wgrad:seg_conv1", "pcs_dgrad_wgrad_folded", ct.byref(fa), L.ptr(WaT), L.ptr(Hs1),
@@ -949,10 +941,8 @@ class Engine:
             L.call("pcs_reduce_partials", L.ptr(Sb), B, 1024, 1.0, L.ptr(colsum), 1024, 1024, s)
         elif self._raw_gram() and sv.a5_colsum is not None:
             # a5 is the activation itself: LDS-DMA Gram; S from conv5's per-chunk column sums
-            nbytes = L.load().pcs_gram_raw_workspace(M, 1024)
-            if nbytes < 0:
-                raise L.PcsError(L.load().pcs_last_error().decode())
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+            nbytes = L.workspace("pcs_gram_raw_workspace", M, 1024)
+            ws =torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
             self._launch("wgrad:global_feat", "pcs_gram_raw", L.ptr(a5), M, 1024, self.a5_dt, L.ptr(ws), nbytes, L.ptr(gram), s)
             cs2 = torch.empty(1024, 2, dtype=torch.float32, device=dev)
             L.call("pcs_reduce_partials", L.ptr(sv.a5_colsum), sv.a5_colsum.shape[0], 2048, 1.0, L.ptr(cs2),

@@ -33,7 +33,7 @@ import torch
 
 from . import _lib as L
 from .data import RaggedBatch
-from .voxel import CH_ALIGN, VoxelBatch, _box, _bf16_2d, _ceil, _pad_channels
+from .voxel import CH_ALIGN, VoxelBatch, _box, _bf16_2d, _conv_operands, _pad_channels, _weight_t, _wgrad
 
 TAPS = 27
 # forward / input gradient through the pair lists (gather-GEMM-reduce) when the map has at most
@@ -53,10 +53,8 @@ def _build_pairs(nmap: torch.Tensor):
     taps + 1 entries."""
     (M, taps), dev = nmap.shape, nmap.device
     st = L.stream_ptr(dev)
-    nb = int(L.load().pcs_sparse_pairs_workspace(M, taps))
-    if nb < 0:
-        raise L.PcsError(L.load().pcs_last_error().decode())
-    ws = torch.empty(max(nb // 4, 1), dtype=torch.int32, device=dev)
+    nb = L.workspace("pcs_sparse_pairs_workspace", M, taps)
+    ws =torch.empty(max(nb // 4, 1), dtype=torch.int32, device=dev)
     counts = torch.empty(taps, dtype=torch.int64, device=dev)
     L.call("pcs_sparse_pairs_count", L.ptr(nmap), M, taps, L.ptr(ws), L.ptr(counts), st)
     tap_off = (ct.c_int64 * (taps + 1))(0, *torch.cumsum(counts, 0).tolist())
@@ -114,10 +112,8 @@ def sparse_from_keys(keys: torch.Tensor, grid: int) -> SparseVoxels:
     # uint64 could equal the EMPTY sentinel) would silently alias rows
     if n and (int(keys.min()) < 0 or torch.unique(keys).numel() != n):
         raise ValueError("sparse_from_keys: keys must be unique and non-negative")
-    cap = int(L.load().pcs_voxel_hash_capacity(n))
-    if cap < 0:
-        raise L.PcsError(L.load().pcs_last_error().decode())
-    tk = torch.empty(cap, dtype=torch.int64, device=dev)
+    cap = L.workspace("pcs_voxel_hash_capacity", n)
+    tk =torch.empty(cap, dtype=torch.int64, device=dev)
     tv = torch.empty(cap, dtype=torch.int32, device=dev)
     st = L.stream_ptr(dev)
     L.call("pcs_voxel_hash_build", L.ptr(keys), n, L.ptr(tk), L.ptr(tv), cap, st)
@@ -138,13 +134,33 @@ def sparse_voxels(rb: RaggedBatch, vb: VoxelBatch, lo=(-1.0, -1.0, -1.0), hi=(1.
     return sparse_from_keys(keys, vb.grid)
 
 
-def _conv_pairs(sv, x, cin, w, cout, bias, y, ydt, flip):
-    """y = the submanifold convolution of x through the pair lists (Z = per-pair products, fp32)."""
-    pin, _, ppos, tap_off, P = sv.pairs()
+def _conv_taps(nmap, pairs, x, cin, w, cout, bias, y, ydt, flip=0):
+    """y[m] = b + sum_t W[tw(t)] x[nmap[m][t]]: through the map's pair lists (pairs; Z = per-pair
+    products, fp32) or, with pairs None, in gathered tiles."""
+    (rows, taps), st = nmap.shape, L.stream_ptr(x.device)
+    if pairs is None:
+        L.call("pcs_sparse_conv", L.ptr(nmap), rows, taps, L.ptr(x), cin, L.ptr(w), cout, L.ptr(bias), L.ptr(y), ydt,
+               flip, st)
+        return
+    pin, _, ppos, tap_off, P = pairs
     z = torch.empty(max(P, 1), cout, dtype=torch.float32, device=x.device)
-    L.call("pcs_sparse_conv_pairs", L.ptr(pin), L.ptr(ppos), ct.addressof(tap_off), TAPS, sv.num_voxels, L.ptr(x), cin,
-           L.ptr(w), cout, L.ptr(bias) if bias is not None else None, L.ptr(z), L.ptr(y), ydt, flip,
-           L.stream_ptr(x.device))
+    L.call("pcs_sparse_conv_pairs", L.ptr(pin), L.ptr(ppos), ct.addressof(tap_off), taps, rows, L.ptr(x), cin, L.ptr(w),
+           cout, L.ptr(bias), L.ptr(z), L.ptr(y), ydt, flip, st)
+
+
+def _sparse_wgrad(nmap, pairs_fn, xk, dyb, cin, cout, has_bias, use_pairs):
+    """(dwk, db) of a convolution through nmap [rows_out, taps], un-padded to cin, cout: over the
+    map's pair lists (pairs_fn()) or in gathered tiles."""
+    (rows, taps), cin_k, cout_k = nmap.shape, xk.shape[1], dyb.shape[1]
+    if use_pairs:
+        pin, pout, _, tap_off, _ = pairs_fn()
+        nbytes = L.workspace("pcs_sparse_conv_wgrad_pairs_workspace", ct.addressof(tap_off), taps, rows, cin_k, cout_k)
+        name, head = "pcs_sparse_conv_wgrad_pairs", (L.ptr(pin), L.ptr(pout), ct.addressof(tap_off), taps, rows)
+    else:
+        nbytes = L.workspace("pcs_sparse_conv_wgrad_workspace", rows, taps, cin_k, cout_k)
+        name, head = "pcs_sparse_conv_wgrad", (L.ptr(nmap), rows, taps)
+    head += (L.ptr(xk), cin_k, L.ptr(dyb), cout_k)
+    return _wgrad(name, head, nbytes, taps, cin, cout, cin_k, cout_k, has_bias, xk.device)
 
 
 class _SubMConvFn(torch.autograd.Function):
@@ -162,24 +178,11 @@ class _SubMConvFn(torch.autograd.Function):
         cout = wk.shape[0]
         if wk.shape[1] != TAPS * cin:
             raise ValueError(f"weight has {wk.shape[1] // TAPS} input channels, x has {cin}")
-        cin_k, cout_k = _ceil(cin), _ceil(cout)
-        xk = _pad_channels(x, cin_k)
-        if (cin_k, cout_k) != (cin, cout):
-            wp = wk.new_zeros(cout_k, TAPS, cin_k)
-            wp[:cout, :, :cin] = wk.reshape(cout, TAPS, cin)
-            wk = wp.reshape(cout_k, TAPS * cin_k)
-        wb = _bf16_2d(wk, cout_k, TAPS * cin_k)
-        bk = None
-        if bias is not None:
-            bk = bias.float().contiguous() if cout_k == cout else _pad_channels(bias.float(), cout_k)
+        xk, wb, bk, cin_k, cout_k = _conv_operands(x, wk, bias, TAPS, CH_ALIGN)
         y = torch.empty(V, cout_k, dtype=out_dtype, device=x.device)
-        ydt = L.BF16 if out_dtype == torch.bfloat16 else L.F32
         pairs = sv.use_pairs()
-        if pairs:
-            _conv_pairs(sv, xk, cin_k, wb, cout_k, bk, y, ydt, 0)
-        else:
-            L.call("pcs_sparse_conv", L.ptr(nbr), V, TAPS, L.ptr(xk), cin_k, L.ptr(wb), cout_k,
-                   L.ptr(bk) if bk is not None else None, L.ptr(y), ydt, 0, L.stream_ptr(x.device))
+        _conv_taps(nbr, sv.pairs() if pairs else None, xk, cin_k, wb, cout_k, bk, y,
+                   L.BF16 if out_dtype == torch.bfloat16 else L.F32)
         ctx.save_for_backward(xk, wb, nbr)
         ctx.sv, ctx.pairs = sv, pairs
         ctx.wpairs = PAIR_WGRAD and V > 0 and cin_k * cout_k <= PAIR_WGRAD_MAX_CH2
@@ -192,41 +195,16 @@ class _SubMConvFn(torch.autograd.Function):
         has_bias, cin, cout = ctx.cfg
         V, cin_k = xk.shape
         cout_k = wb.shape[0]
-        dev, st = xk.device, L.stream_ptr(xk.device)
         dyb = _bf16_2d(_pad_channels(dy, cout_k), V, cout_k)
         dx = dwk = db = None
         if ctx.needs_input_grad[0]:
-            wt = torch.empty(cin_k, TAPS * cout_k, dtype=torch.bfloat16, device=dev)
-            L.call("pcs_conv3d_weight_t", L.ptr(wb), cout_k, TAPS, cin_k, L.ptr(wt), st)
-            dx = torch.empty(V, cin_k, dtype=torch.bfloat16, device=dev)
-            if ctx.pairs:
-                _conv_pairs(ctx.sv, dyb, cout_k, wt, cin_k, None, dx, L.BF16, 1)
-            else:
-                L.call("pcs_sparse_conv", L.ptr(nbr), V, TAPS, L.ptr(dyb), cout_k, L.ptr(wt), cin_k, None, L.ptr(dx),
-                       L.BF16, 1, st)
+            dx = torch.empty(V, cin_k, dtype=torch.bfloat16, device=xk.device)
+            _conv_taps(nbr, ctx.sv.pairs() if ctx.pairs else None, dyb, cout_k, _weight_t(wb, TAPS), cin_k, None, dx,
+                       L.BF16, 1)
             if cin_k != cin:
                 dx = dx[:, :cin].contiguous()
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            if ctx.wpairs:
-                pin, pout, _, tap_off, _ = ctx.sv.pairs()
-                nbytes = int(L.load().pcs_sparse_conv_wgrad_pairs_workspace(ct.addressof(tap_off), TAPS, V, cin_k,
-                                                                            cout_k))
-            else:
-                nbytes = int(L.load().pcs_sparse_conv_wgrad_workspace(V, TAPS, cin_k, cout_k))
-            if nbytes < 0:
-                raise L.PcsError(L.load().pcs_last_error().decode())
-            ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
-            dwk = torch.empty(cout_k, TAPS * cin_k, dtype=torch.float32, device=dev)
-            db = torch.empty(cout_k, dtype=torch.float32, device=dev) if has_bias else None
-            if ctx.wpairs:
-                L.call("pcs_sparse_conv_wgrad_pairs", L.ptr(pin), L.ptr(pout), ct.addressof(tap_off), TAPS, V, L.ptr(xk),
-                       cin_k, L.ptr(dyb), cout_k, L.ptr(ws), nbytes, L.ptr(dwk), L.ptr(db), st)
-            else:
-                L.call("pcs_sparse_conv_wgrad", L.ptr(nbr), V, TAPS, L.ptr(xk), cin_k, L.ptr(dyb), cout_k, L.ptr(ws),
-                       nbytes, L.ptr(dwk), L.ptr(db), st)
-            if (cin_k, cout_k) != (cin, cout):
-                dwk = dwk.reshape(cout_k, TAPS, cin_k)[:cout, :, :cin].reshape(cout, TAPS * cin)
-                db = db[:cout] if db is not None else None
+            dwk, db = _sparse_wgrad(nbr, ctx.sv.pairs, xk, dyb, cin, cout, has_bias, ctx.wpairs)
         return dx, dwk, db, None, None
 
 
@@ -318,20 +296,12 @@ def _conv_rows(link, x, cin, w, cout, bias, y, ydt):
     pin, pout, _, tap_off, P = link.up_pairs()
     assert P == link.fine, "the up map has one pair per fine voxel"
     L.call("pcs_sparse_conv_rows", L.ptr(pin), L.ptr(pout), ct.addressof(tap_off), K2_TAPS, link.fine, L.ptr(x), cin,
-           L.ptr(w), cout, L.ptr(bias) if bias is not None else None, L.ptr(y), ydt, L.stream_ptr(x.device))
+           L.ptr(w), cout, L.ptr(bias), L.ptr(y), ydt, L.stream_ptr(x.device))
 
 
 def _conv_cells(link, x, cin, w, cout, bias, y, ydt):
     """y[m] = b + sum_t W[t] x[child[m][t]]: the 8-tap gather, through the pair lists or in tiles."""
-    st = L.stream_ptr(x.device)
-    if link.use_pairs():
-        pin, _, ppos, tap_off, P = link.down_pairs()
-        z = torch.empty(max(P, 1), cout, dtype=torch.float32, device=x.device)
-        L.call("pcs_sparse_conv_pairs", L.ptr(pin), L.ptr(ppos), ct.addressof(tap_off), K2_TAPS, link.coarse, L.ptr(x),
-               cin, L.ptr(w), cout, L.ptr(bias) if bias is not None else None, L.ptr(z), L.ptr(y), ydt, 0, st)
-    else:
-        L.call("pcs_sparse_conv", L.ptr(link.child), link.coarse, K2_TAPS, L.ptr(x), cin, L.ptr(w), cout,
-               L.ptr(bias) if bias is not None else None, L.ptr(y), ydt, 0, st)
+    _conv_taps(link.child, link.down_pairs() if link.use_pairs() else None, x, cin, w, cout, bias, y, ydt)
 
 
 class _StrideConvFn(torch.autograd.Function):
@@ -351,16 +321,7 @@ class _StrideConvFn(torch.autograd.Function):
         cin, cout = x.shape[1], wk.shape[0]
         if wk.shape[1] != K2_TAPS * cin:
             raise ValueError(f"weight has {wk.shape[1] // K2_TAPS} input channels, x has {cin}")
-        cin_k, cout_k = _ceil(cin), _ceil(cout)
-        xk = _pad_channels(x, cin_k)
-        if (cin_k, cout_k) != (cin, cout):
-            wp = wk.new_zeros(cout_k, K2_TAPS, cin_k)
-            wp[:cout, :, :cin] = wk.reshape(cout, K2_TAPS, cin)
-            wk = wp.reshape(cout_k, K2_TAPS * cin_k)
-        wb = _bf16_2d(wk, cout_k, K2_TAPS * cin_k)
-        bk = None
-        if bias is not None:
-            bk = bias.float().contiguous() if cout_k == cout else _pad_channels(bias.float(), cout_k)
+        xk, wb, bk, cin_k, cout_k = _conv_operands(x, wk, bias, K2_TAPS, CH_ALIGN)
         y = torch.empty(rows_out, cout_k, dtype=out_dtype, device=x.device)
         ydt = L.BF16 if out_dtype == torch.bfloat16 else L.F32
         (_conv_rows if up else _conv_cells)(link, xk, cin_k, wb, cout_k, bk, y, ydt)
@@ -380,38 +341,16 @@ class _StrideConvFn(torch.autograd.Function):
         rows_in, cin_k = xk.shape
         rows_out = link.fine if up else link.coarse
         cout_k = wb.shape[0]
-        dev, st = xk.device, L.stream_ptr(xk.device)
         dyb = _bf16_2d(_pad_channels(dy, cout_k), rows_out, cout_k)
         dx = dwk = db = None
         if ctx.needs_input_grad[0]:
-            wt = torch.empty(cin_k, K2_TAPS * cout_k, dtype=torch.bfloat16, device=dev)
-            L.call("pcs_conv3d_weight_t", L.ptr(wb), cout_k, K2_TAPS, cin_k, L.ptr(wt), st)
-            dx = torch.empty(rows_in, cin_k, dtype=torch.bfloat16, device=dev)
-            (_conv_cells if up else _conv_rows)(link, dyb, cout_k, wt, cin_k, None, dx, L.BF16)
+            dx = torch.empty(rows_in, cin_k, dtype=torch.bfloat16, device=xk.device)
+            (_conv_cells if up else _conv_rows)(link, dyb, cout_k, _weight_t(wb, K2_TAPS), cin_k, None, dx, L.BF16)
             if cin_k != cin:
                 dx = dx[:, :cin].contiguous()
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            nmap = link.up if up else link.child
-            if ctx.wpairs:
-                pin, pout, _, tap_off, _ = link.up_pairs() if up else link.down_pairs()
-                nbytes = int(L.load().pcs_sparse_conv_wgrad_pairs_workspace(ct.addressof(tap_off), K2_TAPS, rows_out,
-                                                                            cin_k, cout_k))
-            else:
-                nbytes = int(L.load().pcs_sparse_conv_wgrad_workspace(rows_out, K2_TAPS, cin_k, cout_k))
-            if nbytes < 0:
-                raise L.PcsError(L.load().pcs_last_error().decode())
-            ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
-            dwk = torch.empty(cout_k, K2_TAPS * cin_k, dtype=torch.float32, device=dev)
-            db = torch.empty(cout_k, dtype=torch.float32, device=dev) if has_bias else None
-            if ctx.wpairs:
-                L.call("pcs_sparse_conv_wgrad_pairs", L.ptr(pin), L.ptr(pout), ct.addressof(tap_off), K2_TAPS, rows_out,
-                       L.ptr(xk), cin_k, L.ptr(dyb), cout_k, L.ptr(ws), nbytes, L.ptr(dwk), L.ptr(db), st)
-            else:
-                L.call("pcs_sparse_conv_wgrad", L.ptr(nmap), rows_out, K2_TAPS, L.ptr(xk), cin_k, L.ptr(dyb), cout_k,
-                       L.ptr(ws), nbytes, L.ptr(dwk), L.ptr(db), st)
-            if (cin_k, cout_k) != (cin, cout):
-                dwk = dwk.reshape(cout_k, K2_TAPS, cin_k)[:cout, :, :cin].reshape(cout, K2_TAPS * cin)
-                db = db[:cout] if db is not None else None
+            dwk, db = _sparse_wgrad(link.up if up else link.child, link.up_pairs if up else link.down_pairs, xk, dyb,
+                                    cin, cout, has_bias, ctx.wpairs)
         return dx, dwk, db, None, None, None
 
 

@@ -45,9 +45,7 @@ def _check_channels(c, x_dtype, out_dtype):
 def _geometry(V, C):
     """(num_blocks, rows_per_block) of the two reductions (pcs_sparse_bn_geometry)."""
     nb = ct.c_int32(0)
-    rpb = int(L.load().pcs_sparse_bn_geometry(V, C, ct.byref(nb)))
-    if rpb < 0:
-        raise L.PcsError(f"pcs_sparse_bn_geometry failed ({rpb}): {L.load().pcs_last_error().decode()}")
+    rpb = L.workspace("pcs_sparse_bn_geometry", V, C, ct.byref(nb))
     return nb.value, rpb
 
 

@@ -152,14 +152,47 @@ def _pad_channels(t, c_to):
     return out
 
 
-class _Conv3dFn(torch.autograd.Function):
-    """y = conv(x, w) + b with w in kernel layout [Cout, taps * Cin] (fp32 master).
+def _conv_operands(x, wk, bias, taps, align):
+    """(xk, wb, bk, cin_k, cout_k) of every convolution here, dense or sparse: channel counts off
+    the align multiple run zero-padded, x with zero input channels, the kernel-layout weight wk
+    [Cout, taps * Cin] (fp32 master; wb in bf16) and the bias with zero output channels, and the
+    padded output / gradient channels are sliced off.  Zero channels contribute exact zeros, so
+    results equal the unpadded convolution's."""
+    cin, cout = x.shape[-1], wk.shape[0]
+    cin_k, cout_k = _ceil(cin, align), _ceil(cout, align)
+    if (cin_k, cout_k) != (cin, cout):
+        wp = wk.new_zeros(cout_k, taps, cin_k)
+        wp[:cout, :, :cin] = wk.reshape(cout, taps, cin)
+        wk = wp.reshape(cout_k, taps * cin_k)
+    bk = None if bias is None else _pad_channels(bias.float(), cout_k)
+    return _pad_channels(x, cin_k), _bf16_2d(wk, cout_k, taps * cin_k), bk, cin_k, cout_k
 
-    Multiples of 32 run natively (a 32-channel U-Net level on 32-channel tiles); other channel
-    counts (a first layer on raw point features) run on zero-padded channels: x and W^T get zero
-    input channels, W and b zero output channels, and the padded output / gradient channels are
-    sliced off.  Zero channels contribute exact zeros, so results equal the unpadded
-    convolution's."""
+
+def _weight_t(wb, taps):
+    """wb [Cout, taps * Cin] transposed per tap (pcs_conv3d_weight_t): an input gradient's weight."""
+    cout_k, cin_k = wb.shape[0], wb.shape[1] // taps
+    wt = torch.empty(cin_k, taps * cout_k, dtype=torch.bfloat16, device=wb.device)
+    L.call("pcs_conv3d_weight_t", L.ptr(wb), cout_k, taps, cin_k, L.ptr(wt), L.stream_ptr(wb.device))
+    return wt
+
+
+def _wgrad(name, head, nbytes, taps, cin, cout, cin_k, cout_k, has_bias, dev):
+    """(dwk, db) of the weight-gradient entry point name(*head, workspace, nbytes, dW, db, stream),
+    without the channels _conv_operands padded."""
+    ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
+    dwk = torch.empty(cout_k, taps * cin_k, dtype=torch.float32, device=dev)
+    db = torch.empty(cout_k, dtype=torch.float32, device=dev) if has_bias else None
+    L.call(name, *head, L.ptr(ws), nbytes, L.ptr(dwk), L.ptr(db), L.stream_ptr(dev))
+    if (cin_k, cout_k) != (cin, cout):
+        dwk = dwk.reshape(cout_k, taps, cin_k)[:cout, :, :cin].reshape(cout, taps * cin)
+        db = db[:cout] if has_bias else None
+    return dwk, db
+
+
+class _Conv3dFn(torch.autograd.Function):
+    """y = conv(x, w) + b with w in kernel layout [Cout, taps * Cin] (fp32 master).  Multiples of
+    32 run natively (a 32-channel U-Net level on 32-channel tiles); other channel counts (a first
+    layer on raw point features) run zero-padded (_conv_operands)."""
 
     @staticmethod
     def forward(ctx, x, wk, bias, k, s, p, transposed, out_dtype, op):
@@ -171,19 +204,10 @@ class _Conv3dFn(torch.autograd.Function):
         cout, taps = wk.shape[0], k ** 3
         if wk.shape[1] != taps * cin:
             raise ValueError(f"weight has {wk.shape[1] // taps} input channels, x has {cin}")
-        cin_k, cout_k = _ceil(cin, DENSE_CH_ALIGN), _ceil(cout, DENSE_CH_ALIGN)
+        xk, wb, bk, cin_k, cout_k = _conv_operands(x, wk, bias, taps, DENSE_CH_ALIGN)
         g = _geom(B, (D, H, W), cin_k, cout_k, k, s, p, transposed, op)
-        xk = _pad_channels(x, cin_k)
-        if (cin_k, cout_k) != (cin, cout):
-            wp = wk.new_zeros(cout_k, taps, cin_k)
-            wp[:cout, :, :cin] = wk.reshape(cout, taps, cin)
-            wk = wp.reshape(cout_k, taps * cin_k)
-        wb = _bf16_2d(wk, cout_k, taps * cin_k)
-        bk = None
-        if bias is not None:
-            bk = bias.float().contiguous() if cout_k == cout else _pad_channels(bias.float(), cout_k)
         y = torch.empty(B, g.Do, g.Ho, g.Wo, cout_k, dtype=out_dtype, device=x.device)
-        L.call("pcs_conv3d", ct.byref(g), L.ptr(xk), L.ptr(wb), L.ptr(bk) if bk is not None else None, L.ptr(y),
+        L.call("pcs_conv3d", ct.byref(g), L.ptr(xk), L.ptr(wb), L.ptr(bk), L.ptr(y),
                L.BF16 if out_dtype == torch.bfloat16 else L.F32, L.stream_ptr(x.device))
         ctx.save_for_backward(xk, wb)
         ctx.cfg = (k, s, p, transposed, bias is not None, op, cin, cout)
@@ -206,8 +230,7 @@ class _Conv3dFn(torch.autograd.Function):
             # (and vice versa): same k, s, p, grids swapped.  A strided convolution whose floor
             # division skipped trailing input planes gets them back as the transposed form's
             # output_padding; a transposed one's own output_padding planes are read as rows of dy.
-            wt = torch.empty(cin_k, taps * cout_k, dtype=torch.bfloat16, device=dev)
-            L.call("pcs_conv3d_weight_t", L.ptr(wb), cout_k, taps, cin_k, L.ptr(wt), st)
+            wt = _weight_t(wb, taps)
             back_op = (0, 0, 0)
             if not transposed:
                 back_op = tuple(d - _out_size(o, k, s, p, True) for d, o in zip((D, H, W), (g.Do, g.Ho, g.Wo)))
@@ -219,16 +242,9 @@ class _Conv3dFn(torch.autograd.Function):
             if cin_k != cin:
                 dx = dx[..., :cin].contiguous()
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            nbytes = L.load().pcs_conv3d_wgrad_workspace(ct.byref(g))
-            if nbytes < 0:
-                raise L.PcsError(L.load().pcs_last_error().decode())
-            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-            dwk = torch.empty(cout_k, taps * cin_k, dtype=torch.float32, device=dev)
-            db = torch.empty(cout_k, dtype=torch.float32, device=dev) if has_bias else None
-            L.call("pcs_conv3d_wgrad", ct.byref(g), L.ptr(xk), L.ptr(dyb), L.ptr(ws), nbytes, L.ptr(dwk), L.ptr(db), st)
-            if (cin_k, cout_k) != (cin, cout):
-                dwk = dwk.reshape(cout_k, taps, cin_k)[:cout, :, :cin].reshape(cout, taps * cin)
-                db = db[:cout] if db is not None else None
+            nbytes = L.workspace("pcs_conv3d_wgrad_workspace", ct.byref(g))
+            dwk, db = _wgrad("pcs_conv3d_wgrad", (ct.byref(g), L.ptr(xk), L.ptr(dyb)), nbytes, taps, cin, cout, cin_k,
+                             cout_k, has_bias, dev)
         return dx, dwk, db, None, None, None, None, None, None
 
 
