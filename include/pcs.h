@@ -795,6 +795,48 @@ int pcs_sparse_conv_wgrad_pairs(const int32_t *pair_in, const int32_t *pair_out,
                                 void *workspace, int64_t workspace_bytes, float *dW, float *db, pcs_stream_t stream);
 
 /*
+ * The two-source sparse convolution: the entry points above on X = [XA | XB] along channels (XA
+ * bf16 [*, CA], XB bf16 [*, CB], both addressed by the same map) without the concatenated array:
+ * a U-Net decoder's convolution of (up, skip).  W is the weight of the concatenated layer, bf16
+ * [Cout][taps][CA + CB].
+ *   Y[m] = b + sum_t ( W[:, tw(t), :CA] XA[nbr[m][t]] + W[:, tw(t), CA:] XB[nbr[m][t]] )
+ * The k-steps run in the order of the concatenated layer and the workspaces are the existing ones
+ * at Cin = CA + CB (pcs_sparse_conv_wgrad_workspace, pcs_sparse_conv_wgrad_pairs_workspace; Z
+ * [P][Cout] f32 of the forward, [P][CA + CB] f32 of the input gradient), so every result is
+ * bit-identical to the single-source call on the concatenated array.
+ * pcs_sparse_conv_cat / _cat_pairs: the forward, Y [M, Cout] in ydtype.
+ * pcs_sparse_conv_cat_dgrad / _cat_dgrad_pairs: the input gradient in one gather pass over dY bf16
+ *   [*, Cout]: with Wt = pcs_conv3d_weight_t(W), bf16 [CA + CB][taps][Cout], and flip = 1, dXA [M, CA]
+ *   and dXB [M, CB] (both in xdtype) are the two column blocks of pcs_sparse_conv(dY, Wt).  (When only
+ *   one block is wanted, call pcs_sparse_conv with the matching row block of Wt.)
+ * pcs_sparse_conv_cat_wgrad / _cat_wgrad_pairs: dW [Cout][taps][CA + CB] f32 and db (may be NULL).
+ * CA, CB and Cout are positive multiples of 64; taps and flip follow pcs_sparse_conv's rules.  Bad
+ * arguments return PCS_EINVAL before any launch.  M == 0 returns 0 and launches nothing: no output
+ * is written (the caller zeroes dW / db of an empty level).
+ */
+int pcs_sparse_conv_cat(const int32_t *nbr, int64_t M, int32_t taps, const void *XA, int32_t CA, const void *XB,
+                        int32_t CB, const void *W, int32_t Cout, const float *bias, void *Y, int32_t ydtype,
+                        int32_t flip, pcs_stream_t stream);
+int pcs_sparse_conv_cat_dgrad(const int32_t *nbr, int64_t M, int32_t taps, const void *dY, int32_t Cout, const void *Wt,
+                              void *dXA, int32_t CA, void *dXB, int32_t CB, int32_t xdtype, int32_t flip,
+                              pcs_stream_t stream);
+int pcs_sparse_conv_cat_wgrad(const int32_t *nbr, int64_t M, int32_t taps, const void *XA, int32_t CA, const void *XB,
+                              int32_t CB, const void *dY, int32_t Cout, void *workspace, int64_t workspace_bytes,
+                              float *dW, float *db, pcs_stream_t stream);
+int pcs_sparse_conv_cat_pairs(const int32_t *pair_in, const int32_t *pair_pos, const int64_t *tap_off, int32_t taps,
+                              int64_t M, const void *XA, int32_t CA, const void *XB, int32_t CB, const void *W,
+                              int32_t Cout, const float *bias, float *Z, void *Y, int32_t ydtype, int32_t flip,
+                              pcs_stream_t stream);
+int pcs_sparse_conv_cat_dgrad_pairs(const int32_t *pair_in, const int32_t *pair_pos, const int64_t *tap_off,
+                                    int32_t taps, int64_t M, const void *dY, int32_t Cout, const void *Wt, float *Z,
+                                    void *dXA, int32_t CA, void *dXB, int32_t CB, int32_t xdtype, int32_t flip,
+                                    pcs_stream_t stream);
+int pcs_sparse_conv_cat_wgrad_pairs(const int32_t *pair_in, const int32_t *pair_out, const int64_t *tap_off,
+                                    int32_t taps, int64_t M, const void *XA, int32_t CA, const void *XB, int32_t CB,
+                                    const void *dY, int32_t Cout, void *workspace, int64_t workspace_bytes, float *dW,
+                                    float *db, pcs_stream_t stream);
+
+/*
  * Point <-> voxel transfer on the occupied-voxel path (csrc/pointvoxel.hip; build-defined, the
  * numpy statement is tests/point_voxel_refs.py): what connects per-point features to any level of
  * the sparse pyramid, forward and backward, without atomics.

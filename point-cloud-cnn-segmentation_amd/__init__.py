@@ -35,6 +35,12 @@ _LAZY = {
     "sparse_batch_norm": ("sparse_norm", "sparse_batch_norm"),
     "SparseBatchNorm": ("sparse_norm", "SparseBatchNorm"),
     "SparseResBlock": ("sparse_norm", "SparseResBlock"),
+    "submanifold_conv3d_cat": ("sparse", "submanifold_conv3d_cat"),
+    "SubMConv3dCat": ("sparse", "SubMConv3dCat"),
+    "SparsePyramid": ("sparse_unet", "SparsePyramid"),
+    "sparse_pyramid": ("sparse_unet", "sparse_pyramid"),
+    "SparseUNet": ("sparse_unet", "SparseUNet"),
+    "SparseUNetSegmentation": ("sparse_unet", "SparseUNetSegmentation"),
 }
 
 

@@ -152,6 +152,16 @@ SIGNATURES = [
     ("pcs_sparse_conv_wgrad_pairs_workspace", _i64, [_vp, _i32, _i64, _i32, _i32]),
     ("pcs_sparse_conv_wgrad_pairs", ct.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp,
                                                _vp]),
+    ("pcs_sparse_conv_cat", ct.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp]),
+    ("pcs_sparse_conv_cat_dgrad", ct.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+    ("pcs_sparse_conv_cat_wgrad", ct.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp,
+                                             _vp]),
+    ("pcs_sparse_conv_cat_pairs", ct.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp,
+                                             _i32, _i32, _vp]),
+    ("pcs_sparse_conv_cat_dgrad_pairs", ct.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32,
+                                                   _i32, _i32, _vp]),
+    ("pcs_sparse_conv_cat_wgrad_pairs", ct.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64,
+                                                   _vp, _vp, _vp]),
     ("pcs_sparse_coarse_keys", ct.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
     ("pcs_sparse_coarse_maps", ct.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("pcs_sparse_conv_rows", ct.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),

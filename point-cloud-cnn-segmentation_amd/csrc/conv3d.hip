@@ -24,6 +24,9 @@
 //     split over row slices with fp32 partials summed in a fixed order (deterministic).
 //     Instantiated by conv3d_wgrad_kernel, sparse_wgrad_kernel (up to TG taps share one dY image)
 //     and pair_wgrad_kernel (one tap's pair list).
+// The sparse kernels take their X operand as one array or as two column blocks (Rows1 / Rows2) and
+// their output likewise (Out1 / Out2): the two-source layer pcs_sparse_conv_cat*, a decoder's
+// convolution of [up | skip] without the concatenated array, in the same k-step order.
 // The 3x3x3 stride-1 stencil has its own halo-staged kernels (stencil3_kernel, stencil3_wgrad_kernel).
 #include "kernel_prims.h"
 
@@ -35,6 +38,47 @@ constexpr int BN = 64, KS = 32;   // output channels per tile, k-step (bf16 elem
 // 16-B slot swizzle of a 64-B LDS row: conflict-free ds_read_b128 fragment reads (rows 4 apart
 // land on different slots of a 256-B bank row)
 PCS_DEV int cswz(int row, int slot) { return slot ^ ((-(row >> 2)) & 3); }
+
+// Where the rows of a gathered X operand live: one [rows, Cin] array (Rows1), or two column blocks
+// [rows, CA] | [rows, Cin - CA] read as their concatenation along channels (Rows2: a U-Net decoder's
+// [up, skip] without the copy).  Arg is what a kernel takes (a plain pointer for one array, so the
+// single-source kernels keep their arguments) and at(X, row, Cin, c) the address of channel c of a
+// row.  c and CA are multiples of 64, the widest channel slice a k-step or a weight-gradient tile
+// reads, so a slice never straddles the blocks and the choice is uniform over the workgroup; the
+// order of k-steps is that of the concatenated array, so the sums are bit-identical to it.
+struct Rows1 {
+  static constexpr bool SPLIT = false;
+  using Arg = const bf16_t *__restrict__;
+  static PCS_DEV const bf16_t *at(const bf16_t *X, int64_t row, int Cin, int c) { return X + row * Cin + c; }
+};
+struct Rows2 {
+  static constexpr bool SPLIT = true;
+  using Arg = Rows2;
+  const bf16_t *XA, *XB;
+  int CA;
+  static PCS_DEV const bf16_t *at(const Rows2 &X, int64_t row, int Cin, int c) {
+    return c < X.CA ? X.XA + row * X.CA + c : X.XB + row * (Cin - X.CA) + (c - X.CA);
+  }
+};
+// The same for an output Y [rows, Cout]: pick(Y, c0, ld) takes the first channel c0 of a 64-channel
+// tile (or 8-channel chunk) and ld = Cout, returns the array that holds it and turns (c0, ld) into
+// the channel and the leading dimension there (Out2: an input gradient written as two column blocks).
+struct Out1 {
+  static constexpr bool SPLIT = false;
+  using Arg = void *__restrict__;
+  static PCS_DEV void *pick(void *Y, int &, int &) { return Y; }
+};
+struct Out2 {
+  static constexpr bool SPLIT = true;
+  using Arg = Out2;
+  void *YA, *YB;
+  int CA;
+  static PCS_DEV void *pick(const Out2 &Y, int &c0, int &ld) {
+    if (c0 < Y.CA) { ld = Y.CA; return Y.YA; }
+    c0 -= Y.CA; ld -= Y.CA;
+    return Y.YB;
+  }
+};
 
 // input voxel feeding output voxel (b, z, y, x) through tap (dz, dy, dx); -1 = none (zero)
 PCS_DEV int64_t in_voxel(const pcs_conv3d_geom &g, int b, int z, int y, int x, int dz, int dy, int dx) {
@@ -128,8 +172,9 @@ PCS_DEV void decode_class(const PClass &q, int64_t u, int &b, int &z, int &y, in
 // the rows of one (tap, channel slice) through registers into swizzled LDS; the next k-step is loaded
 // while the MFMAs of this one run, one barrier per k-step.  Lane (lr, lg) of wave (wr, wc) ends
 // with row wr BMT/2 + 16 i + lr, channels n0 + wc BNT/2 + 16 j + 4 lg .. + 3 in acc[i][j].
-template <int BMT, int KST, int BNT, class RowF, class TapF>
-PCS_DEV void gather_gemm_tile(const bf16_t *__restrict__ X, int Cin, const bf16_t *__restrict__ W, int taps, int n0,
+// XF is Rows1 or Rows2 (Cin = all its channels, the weight's).
+template <int BMT, int KST, int BNT, class XF, class RowF, class TapF>
+PCS_DEV void gather_gemm_tile(typename XF::Arg X, int Cin, const bf16_t *__restrict__ W, int taps, int n0,
                               int nrun, RowF in_row, TapF wtap, f32x4 (&acc_out)[BMT / 32][BNT / 32]) {
   constexpr int RB = KST * 2;          // LDS row bytes
   constexpr int CPR = KST / 8;         // 16-B chunks per row
@@ -155,7 +200,7 @@ PCS_DEV void gather_gemm_tile(const bf16_t *__restrict__ X, int Cin, const bf16_
 #pragma unroll
     for (int h = 0; h < HA; ++h) {
       const int64_t iv = in_row(h, srow + RPP * h, lj);
-      ra[h] = iv >= 0 ? *reinterpret_cast<const u32x4 *>(X + iv * Cin + lc + q * 8) : mk_u32x4(0, 0, 0, 0);
+      ra[h] = iv >= 0 ? *reinterpret_cast<const u32x4 *>(XF::at(X, iv, Cin, lc) + q * 8) : mk_u32x4(0, 0, 0, 0);
     }
 #pragma unroll
     for (int h = 0; h < HB; ++h)
@@ -297,7 +342,7 @@ __global__ __launch_bounds__(THREADS) void conv3d_kernel(pcs_conv3d_geom g, cons
     return (dz * k + dy) * k + dx;
   };
   f32x4 acc[BMT / 32][BNT / 32];
-  gather_gemm_tile<BMT, KST, BNT>(X, g.Cin, W, taps, n0, cm ? pc.ntz * pc.nty * pc.ntx : taps, in_row, wtap, acc);
+  gather_gemm_tile<BMT, KST, BNT, Rows1>(X, g.Cin, W, taps, n0, cm ? pc.ntz * pc.nty * pc.ntx : taps, in_row, wtap, acc);
   auto out_row = [&](int r) -> int64_t {
     const int64_t uo = m0 + r;
     if (uo >= Mrows) return -1;
@@ -778,11 +823,12 @@ __global__ __launch_bounds__(256) void conv3d_weight_t_kernel(const bf16_t *__re
 //   Y[m] = b + sum_t W[tw(t)] X[nbr[m][t]],  tw(t) = flip ? taps - 1 - t : t
 // With flip and W^T (pcs_conv3d_weight_t) this is the input gradient: offset(taps-1-t) =
 // -offset(t) for the centred 3x3x3 taps, so dX[n] = sum_t W_t^T dY[nbr[n][taps-1-t]].
-template <int BMT, int KST, bool OUT_BF16>
+// X: Rows1 or Rows2 (the two-source forward), Y: Out1 or Out2 (its input gradient to both sources).
+template <int BMT, int KST, bool OUT_BF16, class XF = Rows1, class YF = Out1>
 __global__ __launch_bounds__(THREADS) void sparse_conv_kernel(const int32_t *__restrict__ nbr, int64_t M, int taps,
-                                                              const bf16_t *__restrict__ X, int Cin,
+                                                              typename XF::Arg X, int Cin,
                                                               const bf16_t *__restrict__ W, int Cout,
-                                                              const float *__restrict__ bias, void *__restrict__ Y,
+                                                              const float *__restrict__ bias, typename YF::Arg Y,
                                                               int flip) {
   __shared__ uint32_t tmask;
   __shared__ int tlist[32];
@@ -811,15 +857,21 @@ __global__ __launch_bounds__(THREADS) void sparse_conv_kernel(const int32_t *__r
   auto in_row = [&](int, int r, int j) { return m0 + r < M ? nbr[(m0 + r) * taps + tlist[j]] : -1; };
   auto wtap = [&](int j) { return flip ? taps - 1 - tlist[j] : tlist[j]; };
   f32x4 acc[BMT / 32][2];
-  gather_gemm_tile<BMT, KST, BN>(X, Cin, W, taps, blockIdx.y * BN, ntl, in_row, wtap, acc);
-  store_tile<BMT, BN, OUT_BF16>(acc, [&](int r) { return m0 + r < M ? m0 + r : -1; }, blockIdx.y * BN, Cout, bias, Y);
+  const int n0 = blockIdx.y * BN;
+  gather_gemm_tile<BMT, KST, BN, XF>(X, Cin, W, taps, n0, ntl, in_row, wtap, acc);
+  int c0 = n0, ld = Cout;
+  void *y = YF::pick(Y, c0, ld);
+  if constexpr (YF::SPLIT) bias = bias ? bias + (n0 - c0) : nullptr;   // store_tile adds bias[c0 + ..]
+  store_tile<BMT, BN, OUT_BF16>(acc, [&](int r) { return m0 + r < M ? m0 + r : -1; }, c0, ld, bias, y);
 }
 
 // weight gradient of the sparse convolution: dW[co][t][ci] = sum_m dY[m][co] X[nbr[m][t]][ci];
 // a workgroup owns a (64 co x 64 ci) tile, TG consecutive taps and a slice of rows (the
 // structure of conv3d_wgrad_kernel with the neighbour map as the index), partials per slice
+// (X: Rows1 or Rows2; the workgroup's ci0 tile selects the source)
+template <class XF = Rows1>
 __global__ __launch_bounds__(THREADS) void sparse_wgrad_kernel(const int32_t *__restrict__ nbr, int64_t M, int taps,
-                                                               const bf16_t *__restrict__ X, int Cin,
+                                                               typename XF::Arg X, int Cin,
                                                                const bf16_t *__restrict__ dY, int Cout,
                                                                float *__restrict__ ws, int64_t vps) {
   const int nco = Cout / 64;
@@ -835,7 +887,7 @@ __global__ __launch_bounds__(THREADS) void sparse_wgrad_kernel(const int32_t *__
     for (int a = 0; a < TG; ++a) {
       if (a < ntg) {
         const int iv = nbr[u * taps + t0 + a];
-        if (iv >= 0) rx[a] = *reinterpret_cast<const u32x4 *>(X + (int64_t)iv * Cin + ci0 + q8 * 8);
+        if (iv >= 0) rx[a] = *reinterpret_cast<const u32x4 *>(XF::at(X, iv, Cin, ci0) + q8 * 8);
       }
     }
   };
@@ -1027,8 +1079,8 @@ __global__ __launch_bounds__(256) void pairs_build_kernel(const int32_t *__restr
 // The tile of the two pair GEMMs below: acc = W[wt] X[pair_in[p]] (gather_gemm_tile on one tap)
 // for the 64 pairs [p0, pend) of tile blockIdx.x, which belongs to tap t (wt = taps - 1 - t under
 // flip), and the 64 output channels from blockIdx.y * BN.
-template <int KST>
-PCS_DEV void pair_tile(const PairTaps &pt, const int32_t *__restrict__ pin, const bf16_t *__restrict__ X, int Cin,
+template <int KST, class XF>
+PCS_DEV void pair_tile(const PairTaps &pt, const int32_t *__restrict__ pin, typename XF::Arg X, int Cin,
                        const bf16_t *__restrict__ W, int flip, f32x4 (&acc)[2][2], int64_t &p0, int64_t &pend) {
   constexpr int RPP = THREADS / (KST / 8), HA = 64 / RPP;   // gather_gemm_tile's staging passes
   const int taps = pt.taps, tile = blockIdx.x;
@@ -1043,16 +1095,16 @@ PCS_DEV void pair_tile(const PairTaps &pt, const int32_t *__restrict__ pin, cons
     iv[h] = p < pend ? pin[p] : -1;
   }
   const int wt = flip ? taps - 1 - t : t;
-  gather_gemm_tile<64, KST, BN>(X, Cin, W, taps, blockIdx.y * BN, 1, [&](int h, int, int) { return iv[h]; },
+  gather_gemm_tile<64, KST, BN, XF>(X, Cin, W, taps, blockIdx.y * BN, 1, [&](int h, int, int) { return iv[h]; },
                                 [&](int) { return wt; }, acc);
 }
 
 // Z[p][n0 ..] = W[tw(t)] X[pair_in[p]] for the 64 pairs of one tile of tap t (fp32 products).
 // (Reducing in the centre tap's GEMM epilogue instead of a separate pass, the centre's products
 // never stored, was slower: 26 dependent gathers per lane there against 8 threads per row here.)
-template <int KST>
+template <int KST, class XF = Rows1>
 __global__ __launch_bounds__(THREADS) void pair_gemm_kernel(PairTaps pt, const int32_t *__restrict__ pin,
-                                                            const bf16_t *__restrict__ X, int Cin,
+                                                            typename XF::Arg X, int Cin,
                                                             const bf16_t *__restrict__ W, int Cout, int flip,
                                                             float *__restrict__ Z) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -1060,7 +1112,7 @@ __global__ __launch_bounds__(THREADS) void pair_gemm_kernel(PairTaps pt, const i
   const int n0 = blockIdx.y * BN;
   f32x4 acc[2][2];
   int64_t p0, pend;
-  pair_tile<KST>(pt, pin, X, Cin, W, flip, acc, p0, pend);
+  pair_tile<KST, XF>(pt, pin, X, Cin, W, flip, acc, p0, pend);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int64_t p = p0 + wr * 32 + i * 16 + lr;
@@ -1074,10 +1126,10 @@ __global__ __launch_bounds__(THREADS) void pair_gemm_kernel(PairTaps pt, const i
 }
 
 // Y[m][c .. c + 7] = b + sum over taps in order of Z[pair_pos[m][t]] (one thread per 8 channels)
-template <bool OUT_BF16>
+template <bool OUT_BF16, class YF = Out1>
 __global__ __launch_bounds__(256) void pair_reduce_kernel(const int32_t *__restrict__ ppos, int64_t M, int taps,
                                                           const float *__restrict__ Z, int Cout,
-                                                          const float *__restrict__ bias, void *__restrict__ Y) {
+                                                          const float *__restrict__ bias, typename YF::Arg Y) {
   const int cpr = Cout / 8;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= M * cpr) return;
@@ -1094,12 +1146,14 @@ __global__ __launch_bounds__(256) void pair_reduce_kernel(const int32_t *__restr
     a += *reinterpret_cast<const f32x4 *>(Z + (int64_t)q * Cout + c);
     b += *reinterpret_cast<const f32x4 *>(Z + (int64_t)q * Cout + c + 4);
   }
+  int cy = c, ld = Cout;
+  void *y = YF::pick(Y, cy, ld);
   if constexpr (OUT_BF16) {
-    *reinterpret_cast<u32x4 *>(reinterpret_cast<bf16_t *>(Y) + m * Cout + c) =
+    *reinterpret_cast<u32x4 *>(reinterpret_cast<bf16_t *>(y) + m * ld + cy) =
         mk_u32x4(pack2bf(a[0], a[1]), pack2bf(a[2], a[3]), pack2bf(b[0], b[1]), pack2bf(b[2], b[3]));
   } else {
-    *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(Y) + m * Cout + c) = a;
-    *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(Y) + m * Cout + c + 4) = b;
+    *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(y) + m * ld + cy) = a;
+    *reinterpret_cast<f32x4 *>(reinterpret_cast<float *>(y) + m * ld + cy + 4) = b;
   }
 }
 
@@ -1116,7 +1170,7 @@ __global__ __launch_bounds__(THREADS) void pair_rows_kernel(PairTaps pt, const i
                                                             void *__restrict__ Y) {
   f32x4 acc[2][2];
   int64_t p0, pend;
-  pair_tile<KST>(pt, pin, X, Cin, W, 0, acc, p0, pend);
+  pair_tile<KST, Rows1>(pt, pin, X, Cin, W, 0, acc, p0, pend);
   auto out_row = [&](int r) -> int64_t {
     if (p0 + r >= pend) return -1;
     const int64_t uo = pout[p0 + r];
@@ -1129,9 +1183,10 @@ __global__ __launch_bounds__(THREADS) void pair_rows_kernel(PairTaps pt, const i
 // ws[g][co][ci] (wgrad_tile with one X image, gathered through the pair list).  Slices are a fixed
 // number of pairs, so a tap's slice count follows its pair count (the centre tap has every row)
 // and every workgroup has about the same work.
+template <class XF = Rows1>
 __global__ __launch_bounds__(THREADS) void pair_wgrad_kernel(PairTaps pt, const int32_t *__restrict__ pin,
                                                              const int32_t *__restrict__ pout,
-                                                             const bf16_t *__restrict__ X, int Cin,
+                                                             typename XF::Arg X, int Cin,
                                                              const bf16_t *__restrict__ dY, int Cout,
                                                              float *__restrict__ ws) {
   const int nco = Cout / 64, taps = pt.taps;
@@ -1146,7 +1201,7 @@ __global__ __launch_bounds__(THREADS) void pair_wgrad_kernel(PairTaps pt, const 
     const int64_t p = lo + (int64_t)ks * WV + sv;
     if (p >= hi) return;
     rd = *reinterpret_cast<const u32x4 *>(dY + (int64_t)pout[p] * Cout + co0 + q8 * 8);
-    rx[0] = *reinterpret_cast<const u32x4 *>(X + (int64_t)pin[p] * Cin + ci0 + q8 * 8);
+    rx[0] = *reinterpret_cast<const u32x4 *>(XF::at(X, pin[p], Cin, ci0) + q8 * 8);
   };
   f32x4 acc[1][2][2];
   wgrad_tile<64, 64, 1>(load_rows, (int)((hi - lo + WV - 1) / WV), 1, acc);   // (uniform; 0 k-steps for an empty slice)
@@ -1189,6 +1244,86 @@ int bias_grad(const void *dY, int Cout, int64_t M, int64_t sp, int64_t vps, floa
   hipLaunchKernelGGL(conv3d_reduce_kernel, dim3((unsigned)((Cout + 255) / 256)), dim3(256), 0, s, wsb, sp, (int64_t)Cout, db);
   e = hipGetLastError();
   return e != hipSuccess ? pcs_set_error(e, who) : 0;
+}
+
+int launched(const char *who) {
+  const hipError_t e = hipGetLastError();
+  return e != hipSuccess ? pcs_set_error(e, who) : 0;
+}
+
+// The launches behind the sparse entry points, after their argument checks: XF is Rows1 or Rows2, YF
+// Out1 or Out2 (the two-source layer's blocks are multiples of 64 channels: 64-deep k-steps).
+
+// sparse_conv_kernel over M > 0 rows
+template <class XF, class YF>
+int launch_sparse_conv(const char *who, const int32_t *nbr, int64_t M, int taps, typename XF::Arg X, int Cin, const void *W,
+                       int Cout, const float *bias, typename YF::Arg Y, int ydtype, int flip, hipStream_t s) {
+  const int64_t tiles = (M + 63) / 64;
+  if (tiles > 0x7fffffff) return pcs_set_einval(who, "too many rows");
+  const dim3 grid((unsigned)tiles, (unsigned)(Cout / BN));
+  const bf16_t *Wb = static_cast<const bf16_t *>(W);
+#define PCS_SC(KST, OB) \
+  hipLaunchKernelGGL((sparse_conv_kernel<64, KST, OB, XF, YF>), grid, dim3(THREADS), 0, s, nbr, M, taps, X, Cin, Wb, \
+                     Cout, bias, Y, flip)
+  if constexpr (XF::SPLIT || YF::SPLIT) {
+    if (ydtype == PCS_BF16) PCS_SC(64, true); else PCS_SC(64, false);
+  } else {
+    PCS_KST_OB(Cin % 64 == 0, ydtype == PCS_BF16, PCS_SC);
+  }
+#undef PCS_SC
+  return launched(who);
+}
+
+// pair_gemm_kernel over the pair tiles into Z, then pair_reduce_kernel over the M rows
+template <class XF, class YF>
+int launch_pair_conv(const char *who, const PairTaps &pt, const int32_t *pair_in, const int32_t *pair_pos, int64_t M,
+                     typename XF::Arg X, int Cin, const void *W, int Cout, const float *bias, float *Z,
+                     typename YF::Arg Y, int ydtype, int flip, hipStream_t s) {
+  const int taps = pt.taps, tiles = pt.tile_off[taps];
+  const bf16_t *Wb = static_cast<const bf16_t *>(W);
+  if (tiles > 0) {
+    const dim3 grid((unsigned)tiles, (unsigned)(Cout / BN));
+    if (XF::SPLIT || Cin % 64 == 0)
+      hipLaunchKernelGGL((pair_gemm_kernel<64, XF>), grid, dim3(THREADS), 0, s, pt, pair_in, X, Cin, Wb, Cout,
+                         flip, Z);
+    else if constexpr (!XF::SPLIT)
+      hipLaunchKernelGGL((pair_gemm_kernel<32, XF>), grid, dim3(THREADS), 0, s, pt, pair_in, X, Cin, Wb, Cout,
+                         flip, Z);
+    if (const int rc = launched(who)) return rc;
+  }
+  const int64_t n = M * (Cout / 8);
+  if (n > 0) {
+    const dim3 g((unsigned)((n + 255) / 256));
+    if (ydtype == PCS_BF16)
+      hipLaunchKernelGGL((pair_reduce_kernel<true, YF>), g, dim3(256), 0, s, pair_pos, M, taps, Z, Cout, bias,
+                         Y);
+    else
+      hipLaunchKernelGGL((pair_reduce_kernel<false, YF>), g, dim3(256), 0, s, pair_pos, M, taps, Z, Cout, bias,
+                         Y);
+    return launched(who);
+  }
+  return 0;
+}
+
+// sparse_wgrad_kernel's slice partials (zeros when M == 0), their sum into dW, and db
+template <class XF>
+int launch_sparse_wgrad(const char *who, const int32_t *nbr, int64_t M, int taps, typename XF::Arg X, int Cin, const void *dY,
+                        int Cout, void *workspace, float *dW, float *db, hipStream_t s) {
+  const int64_t sp = sparse_wgrad_splits(M, taps, Cin, Cout);
+  const int64_t vps = ((M + sp - 1) / sp + WV - 1) / WV * WV;
+  const int64_t wlen = (int64_t)Cout * taps * Cin;
+  float *ws = static_cast<float *>(workspace), *wsb = ws + sp * wlen;
+  if (M > 0) {
+    hipLaunchKernelGGL(sparse_wgrad_kernel<XF>, dim3((unsigned)((Cout / 64) * (Cin / 64)), (unsigned)((taps + TG - 1) / TG), (unsigned)sp),
+                       dim3(THREADS), 0, s, nbr, M, taps, X, Cin, static_cast<const bf16_t *>(dY), Cout, ws, vps);
+  } else {
+    const hipError_t e = hipMemsetAsync(ws, 0, sp * wlen * 4, s);
+    if (e != hipSuccess) return pcs_set_error(e, who);
+  }
+  if (const int rc = launched(who)) return rc;
+  hipLaunchKernelGGL(conv3d_reduce_kernel, dim3((unsigned)((wlen + 255) / 256)), dim3(256), 0, s, ws, sp, wlen, dW);
+  if (const int rc = launched(who)) return rc;
+  return db ? bias_grad(dY, Cout, M, sp, vps, wsb, db, s, who) : 0;
 }
 
 }  // namespace
@@ -1310,18 +1445,8 @@ extern "C" int pcs_sparse_conv(const int32_t *nbr, int64_t M, int32_t taps, cons
   if (flip != 0 && taps != 27 && taps != 1)
     return pcs_set_einval("pcs_sparse_conv", "flip needs the centred 27-tap neighbour map (or taps == 1)");
   if (M == 0) return 0;
-  const int64_t tiles = (M + 63) / 64;
-  if (tiles > 0x7fffffff) return pcs_set_einval("pcs_sparse_conv", "too many rows");
-  const dim3 grid((unsigned)tiles, (unsigned)(Cout / BN));
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bf16_t *Xb = static_cast<const bf16_t *>(X), *Wb = static_cast<const bf16_t *>(W);
-#define PCS_SC(KST, OB) \
-  hipLaunchKernelGGL((sparse_conv_kernel<64, KST, OB>), grid, dim3(THREADS), 0, s, nbr, M, (int)taps, Xb, (int)Cin, Wb, \
-                     (int)Cout, bias, Y, (int)flip)
-  PCS_KST_OB(Cin % 64 == 0, ydtype == PCS_BF16, PCS_SC);
-#undef PCS_SC
-  PCS_CHECK_LAUNCH();
-  return 0;
+  return launch_sparse_conv<Rows1, Out1>(__func__, nbr, M, taps, static_cast<const bf16_t *>(X), Cin, W, Cout, bias, Y, ydtype,
+                            flip, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int64_t pcs_sparse_conv_wgrad_workspace(int64_t M, int32_t taps, int32_t Cin, int32_t Cout) {
@@ -1338,23 +1463,8 @@ extern "C" int pcs_sparse_conv_wgrad(const int32_t *nbr, int64_t M, int32_t taps
   if (need < 0) return (int)need;
   if (!nbr || !X || !dY || !dW || !workspace || workspace_bytes < need)
     return pcs_set_einval("pcs_sparse_conv_wgrad", "nbr, X, dY, dW and a workspace of pcs_sparse_conv_wgrad_workspace bytes");
-  const int64_t sp = sparse_wgrad_splits(M, taps, Cin, Cout);
-  const int64_t vps = ((M + sp - 1) / sp + WV - 1) / WV * WV;
-  const int64_t wlen = (int64_t)Cout * taps * Cin;
-  float *ws = static_cast<float *>(workspace), *wsb = ws + sp * wlen;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (M > 0) {
-    hipLaunchKernelGGL(sparse_wgrad_kernel, dim3((unsigned)((Cout / 64) * (Cin / 64)), (unsigned)((taps + TG - 1) / TG), (unsigned)sp),
-                       dim3(THREADS), 0, s, nbr, M, (int)taps, static_cast<const bf16_t *>(X), (int)Cin,
-                       static_cast<const bf16_t *>(dY), (int)Cout, ws, vps);
-  } else {
-    const hipError_t e = hipMemsetAsync(ws, 0, sp * wlen * 4, s);
-    if (e != hipSuccess) return pcs_set_error(e, "pcs_sparse_conv_wgrad");
-  }
-  PCS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(conv3d_reduce_kernel, dim3((unsigned)((wlen + 255) / 256)), dim3(256), 0, s, ws, sp, wlen, dW);
-  PCS_CHECK_LAUNCH();
-  return db ? bias_grad(dY, Cout, M, sp, vps, wsb, db, s, __func__) : 0;
+  return launch_sparse_wgrad<Rows1>(__func__, nbr, M, taps, static_cast<const bf16_t *>(X), Cin, dY, Cout, workspace, dW, db,
+                             reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- per-tap pair lists (see pairs_count_kernel)
@@ -1423,23 +1533,8 @@ extern "C" int pcs_sparse_conv_pairs(const int32_t *pair_in, const int32_t *pair
     return pcs_set_einval("pcs_sparse_conv_pairs", "bad arguments (Cin % 32 == 0, Cout % 64 == 0, Y f32 | bf16, Z [P, Cout] f32)");
   if (flip && taps != 27 && taps != 1)
     return pcs_set_einval("pcs_sparse_conv_pairs", "flip needs the centred 27-tap neighbour map (or taps == 1)");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int tiles = pt.tile_off[taps];
-  const bf16_t *Xb = static_cast<const bf16_t *>(X), *Wb = static_cast<const bf16_t *>(W);
-  if (tiles > 0) {
-    const dim3 grid((unsigned)tiles, (unsigned)(Cout / BN));
-    if (Cin % 64 == 0) hipLaunchKernelGGL(pair_gemm_kernel<64>, grid, dim3(THREADS), 0, s, pt, pair_in, Xb, (int)Cin, Wb, (int)Cout, (int)flip, Z);
-    else hipLaunchKernelGGL(pair_gemm_kernel<32>, grid, dim3(THREADS), 0, s, pt, pair_in, Xb, (int)Cin, Wb, (int)Cout, (int)flip, Z);
-    PCS_CHECK_LAUNCH();
-  }
-  const int64_t n = M * (Cout / 8);
-  if (n > 0) {
-    const dim3 g((unsigned)((n + 255) / 256));
-    if (ydtype == PCS_BF16) hipLaunchKernelGGL(pair_reduce_kernel<true>, g, dim3(256), 0, s, pair_pos, M, (int)taps, Z, (int)Cout, bias, Y);
-    else hipLaunchKernelGGL(pair_reduce_kernel<false>, g, dim3(256), 0, s, pair_pos, M, (int)taps, Z, (int)Cout, bias, Y);
-    PCS_CHECK_LAUNCH();
-  }
-  return 0;
+  return launch_pair_conv<Rows1, Out1>(__func__, pt, pair_in, pair_pos, M, static_cast<const bf16_t *>(X), Cin, W, Cout, bias,
+                                       Z, Y, ydtype, flip, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int pcs_sparse_conv_rows(const int32_t *pair_in, const int32_t *pair_out, const int64_t *tap_off, int32_t taps,
@@ -1489,6 +1584,23 @@ void pair_wgrad_slices(PairTaps *pt, int Cin, int Cout) {
     }
   }
 }
+
+// pair_wgrad_kernel's slice partials (pt with its slices), their sum into dW, and db
+template <class XF>
+int launch_pair_wgrad(const char *who, const PairTaps &pt, const int32_t *pair_in, const int32_t *pair_out, int64_t M,
+                      typename XF::Arg X, int Cin, const void *dY, int Cout, void *workspace, float *dW, float *db, hipStream_t s) {
+  const int taps = pt.taps;
+  const int64_t ns = pt.slice_off[taps], wlen = (int64_t)Cout * taps * Cin;
+  float *ws = static_cast<float *>(workspace), *wsb = ws + ns * Cout * Cin;
+  hipLaunchKernelGGL(pair_wgrad_kernel<XF>, dim3((unsigned)((Cout / 64) * (Cin / 64)), (unsigned)ns), dim3(THREADS), 0, s, pt,
+                     pair_in, pair_out, X, Cin, static_cast<const bf16_t *>(dY), Cout, ws);
+  if (const int rc = launched(who)) return rc;
+  hipLaunchKernelGGL(pair_wgrad_reduce_kernel, dim3((unsigned)((wlen + 255) / 256)), dim3(256), 0, s, pt, ws, Cin, Cout, dW);
+  if (const int rc = launched(who)) return rc;
+  if (!db) return 0;
+  const int64_t spb = sparse_wgrad_splits(M, 1, 64, Cout);
+  return bias_grad(dY, Cout, M, spb, ((M + spb - 1) / spb + WV - 1) / WV * WV, wsb, db, s, who);
+}
 }  // namespace
 
 extern "C" int64_t pcs_sparse_conv_wgrad_pairs_workspace(const int64_t *tap_off, int32_t taps, int64_t M, int32_t Cin,
@@ -1514,15 +1626,105 @@ extern "C" int pcs_sparse_conv_wgrad_pairs(const int32_t *pair_in, const int32_t
   PairTaps pt;
   pair_taps(tap_off, taps, &pt);
   pair_wgrad_slices(&pt, Cin, Cout);
-  const int64_t ns = pt.slice_off[taps], wlen = (int64_t)Cout * taps * Cin;
-  float *ws = static_cast<float *>(workspace), *wsb = ws + ns * Cout * Cin;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(pair_wgrad_kernel, dim3((unsigned)((Cout / 64) * (Cin / 64)), (unsigned)ns), dim3(THREADS), 0, s,
-                     pt, pair_in, pair_out, static_cast<const bf16_t *>(X), (int)Cin, static_cast<const bf16_t *>(dY), (int)Cout, ws);
-  PCS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(pair_wgrad_reduce_kernel, dim3((unsigned)((wlen + 255) / 256)), dim3(256), 0, s, pt, ws, (int)Cin, (int)Cout, dW);
-  PCS_CHECK_LAUNCH();
-  if (!db) return 0;
-  const int64_t spb = sparse_wgrad_splits(M, 1, 64, Cout);
-  return bias_grad(dY, Cout, M, spb, ((M + spb - 1) / spb + WV - 1) / WV * WV, wsb, db, s, __func__);
+  return launch_pair_wgrad<Rows1>(__func__, pt, pair_in, pair_out, M, static_cast<const bf16_t *>(X), Cin, dY, Cout, workspace,
+                           dW, db, reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- the two-source layer: the kernels above on X = [XA | XB] along channels, never materialised
+// (Rows2 / Out2).  Same k-step order, split geometry and workspaces as the layer on the
+// concatenated array (Cin = CA + CB), so every result is bit-identical to it.
+namespace {
+// the rules the six entry points share, or nullptr
+const char *cat_args_bad(int64_t M, int taps, int CA, int CB, int Cout, int ydtype, int flip) {
+  if (M < 0) return "M must be >= 0";
+  if (taps < 1 || taps > PT_MAX) return "1 <= taps <= 27";
+  if (CA <= 0 || CB <= 0 || Cout <= 0 || CA % 64 != 0 || CB % 64 != 0 || Cout % 64 != 0 || (int64_t)CA + CB > (1 << 20) ||
+      Cout > (1 << 20))
+    return "CA, CB and Cout must be positive multiples of 64";
+  if (ydtype != PCS_F32 && ydtype != PCS_BF16) return "output dtype: PCS_F32 or PCS_BF16";
+  if (flip != 0 && flip != 1) return "flip must be 0 or 1";
+  if (flip && taps != 27 && taps != 1) return "flip needs the centred 27-tap neighbour map (or taps == 1)";
+  return nullptr;
+}
+Rows2 rows2(const void *XA, int CA, const void *XB) {
+  return Rows2{static_cast<const bf16_t *>(XA), static_cast<const bf16_t *>(XB), CA};
+}
+}  // namespace
+
+extern "C" int pcs_sparse_conv_cat(const int32_t *nbr, int64_t M, int32_t taps, const void *XA, int32_t CA, const void *XB,
+                                   int32_t CB, const void *W, int32_t Cout, const float *bias, void *Y, int32_t ydtype,
+                                   int32_t flip, pcs_stream_t stream) {
+  if (const char *why = cat_args_bad(M, taps, CA, CB, Cout, ydtype, flip)) return pcs_set_einval(__func__, why);
+  if (!nbr || !XA || !XB || !W || !Y) return pcs_set_einval(__func__, "NULL nbr, XA, XB, W or Y");
+  if (M == 0) return 0;
+  return launch_sparse_conv<Rows2, Out1>(__func__, nbr, M, taps, rows2(XA, CA, XB), CA + CB, W, Cout, bias, Y, ydtype, flip,
+                            reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int pcs_sparse_conv_cat_dgrad(const int32_t *nbr, int64_t M, int32_t taps, const void *dY, int32_t Cout,
+                                         const void *Wt, void *dXA, int32_t CA, void *dXB, int32_t CB, int32_t xdtype,
+                                         int32_t flip, pcs_stream_t stream) {
+  if (const char *why = cat_args_bad(M, taps, CA, CB, Cout, xdtype, flip)) return pcs_set_einval(__func__, why);
+  if (!nbr || !dY || !Wt || !dXA || !dXB) return pcs_set_einval(__func__, "NULL nbr, dY, Wt, dXA or dXB");
+  if (M == 0) return 0;
+  return launch_sparse_conv<Rows1, Out2>(__func__, nbr, M, taps, static_cast<const bf16_t *>(dY), Cout, Wt, CA + CB, nullptr,
+                            Out2{dXA, dXB, CA}, xdtype, flip, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int pcs_sparse_conv_cat_wgrad(const int32_t *nbr, int64_t M, int32_t taps, const void *XA, int32_t CA,
+                                         const void *XB, int32_t CB, const void *dY, int32_t Cout, void *workspace,
+                                         int64_t workspace_bytes, float *dW, float *db, pcs_stream_t stream) {
+  if (const char *why = cat_args_bad(M, taps, CA, CB, Cout, PCS_BF16, 0)) return pcs_set_einval(__func__, why);
+  if (!nbr || !XA || !XB || !dY || !dW || !workspace) return pcs_set_einval(__func__, "NULL nbr, XA, XB, dY, dW or workspace");
+  if (workspace_bytes < pcs_sparse_conv_wgrad_workspace(M, taps, CA + CB, Cout))
+    return pcs_set_einval(__func__, "the workspace is shorter than pcs_sparse_conv_wgrad_workspace(M, taps, CA + CB, Cout)");
+  if (M == 0) return 0;
+  return launch_sparse_wgrad<Rows2>(__func__, nbr, M, taps, rows2(XA, CA, XB), CA + CB, dY, Cout, workspace, dW, db,
+                             reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int pcs_sparse_conv_cat_pairs(const int32_t *pair_in, const int32_t *pair_pos, const int64_t *tap_off,
+                                         int32_t taps, int64_t M, const void *XA, int32_t CA, const void *XB, int32_t CB,
+                                         const void *W, int32_t Cout, const float *bias, float *Z, void *Y, int32_t ydtype,
+                                         int32_t flip, pcs_stream_t stream) {
+  if (const char *why = cat_args_bad(M, taps, CA, CB, Cout, ydtype, flip)) return pcs_set_einval(__func__, why);
+  PairTaps pt;
+  if (const char *why = pair_taps(tap_off, taps, &pt)) return pcs_set_einval(__func__, why);
+  if (!pair_pos || !XA || !XB || !W || !Y || (tap_off[taps] > 0 && (!pair_in || !Z)))
+    return pcs_set_einval(__func__, "NULL pair_pos, XA, XB, W or Y (or pair_in, Z with pairs)");
+  if (M == 0) return 0;
+  return launch_pair_conv<Rows2, Out1>(__func__, pt, pair_in, pair_pos, M, rows2(XA, CA, XB), CA + CB, W, Cout, bias, Z, Y, ydtype,
+                          flip, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int pcs_sparse_conv_cat_dgrad_pairs(const int32_t *pair_in, const int32_t *pair_pos, const int64_t *tap_off,
+                                               int32_t taps, int64_t M, const void *dY, int32_t Cout, const void *Wt,
+                                               float *Z, void *dXA, int32_t CA, void *dXB, int32_t CB, int32_t xdtype,
+                                               int32_t flip, pcs_stream_t stream) {
+  if (const char *why = cat_args_bad(M, taps, CA, CB, Cout, xdtype, flip)) return pcs_set_einval(__func__, why);
+  PairTaps pt;
+  if (const char *why = pair_taps(tap_off, taps, &pt)) return pcs_set_einval(__func__, why);
+  if (!pair_pos || !dY || !Wt || !dXA || !dXB || (tap_off[taps] > 0 && (!pair_in || !Z)))
+    return pcs_set_einval(__func__, "NULL pair_pos, dY, Wt, dXA or dXB (or pair_in, Z with pairs)");
+  if (M == 0) return 0;
+  return launch_pair_conv<Rows1, Out2>(__func__, pt, pair_in, pair_pos, M, static_cast<const bf16_t *>(dY), Cout, Wt, CA + CB,
+                          nullptr, Z, Out2{dXA, dXB, CA}, xdtype, flip, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int pcs_sparse_conv_cat_wgrad_pairs(const int32_t *pair_in, const int32_t *pair_out, const int64_t *tap_off,
+                                               int32_t taps, int64_t M, const void *XA, int32_t CA, const void *XB,
+                                               int32_t CB, const void *dY, int32_t Cout, void *workspace,
+                                               int64_t workspace_bytes, float *dW, float *db, pcs_stream_t stream) {
+  if (const char *why = cat_args_bad(M, taps, CA, CB, Cout, PCS_BF16, 0)) return pcs_set_einval(__func__, why);
+  PairTaps pt;
+  if (const char *why = pair_taps(tap_off, taps, &pt)) return pcs_set_einval(__func__, why);
+  if (!XA || !XB || !dY || !dW || !workspace || (tap_off[taps] > 0 && (!pair_in || !pair_out)))
+    return pcs_set_einval(__func__, "NULL XA, XB, dY, dW or workspace (or pair_in, pair_out with pairs)");
+  if (workspace_bytes < pcs_sparse_conv_wgrad_pairs_workspace(tap_off, taps, M, CA + CB, Cout))
+    return pcs_set_einval(__func__,
+                          "the workspace is shorter than pcs_sparse_conv_wgrad_pairs_workspace(tap_off, taps, M, CA + CB, Cout)");
+  if (M == 0) return 0;
+  pair_wgrad_slices(&pt, CA + CB, Cout);
+  return launch_pair_wgrad<Rows2>(__func__, pt, pair_in, pair_out, M, rows2(XA, CA, XB), CA + CB, dY, Cout, workspace, dW, db,
+                           reinterpret_cast<hipStream_t>(stream));
 }

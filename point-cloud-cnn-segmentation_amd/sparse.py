@@ -23,6 +23,15 @@ A U-Net changes resolution with the 2x2x2, stride-2 pair, still on occupied voxe
 The down forward and the up input gradient are the 8-tap gather through link.child (the kernels
 above at taps = 8); the up forward and the down input gradient have one tap per output row and
 run pcs_sparse_conv_rows, which writes each row once from its own tap's GEMM tile.
+
+The decoder's skip connection convolves (up, skip) without concatenating them:
+
+    m = SubMConv3dCat(64, 64, 64)(u, e, sv)              # == SubMConv3d(128, 64)(torch.cat([u, e], 1), sv)
+
+The kernels read the two arrays as the column blocks of one X operand (pcs_sparse_conv_cat*), in
+the concatenated layer's k-step order, so the result is bit-identical to it; no [V, CA + CB]
+tensor is written, kept for the backward or sliced into gradients.  sparse_unet.py assembles the
+levels (SparsePyramid) and these layers into the occupied-voxel U-Net.
 """
 from __future__ import annotations
 
@@ -232,6 +241,149 @@ class SubMConv3d(torch.nn.Module):
         return submanifold_conv3d(x, self.weight, sv, self.bias, out_dtype)
 
 
+# ---- the two-source layer: the submanifold convolution of [xa | xb] without the concatenation
+def _conv_taps_cat(nmap, pairs, xa, ca, xb, cb, w, cout, bias, y, ydt):
+    """_conv_taps on x = [xa | xb] along channels (pcs_sparse_conv_cat, pcs_sparse_conv_cat_pairs)."""
+    (rows, taps), st = nmap.shape, L.stream_ptr(xa.device)
+    if pairs is None:
+        L.call("pcs_sparse_conv_cat", L.ptr(nmap), rows, taps, L.ptr(xa), ca, L.ptr(xb), cb, L.ptr(w), cout, L.ptr(bias),
+               L.ptr(y), ydt, 0, st)
+        return
+    pin, _, ppos, tap_off, P = pairs
+    z = torch.empty(max(P, 1), cout, dtype=torch.float32, device=xa.device)
+    L.call("pcs_sparse_conv_cat_pairs", L.ptr(pin), L.ptr(ppos), ct.addressof(tap_off), taps, rows, L.ptr(xa), ca, L.ptr(xb),
+           cb, L.ptr(w), cout, L.ptr(bias), L.ptr(z), L.ptr(y), ydt, 0, st)
+
+
+def _dgrad_taps_cat(nmap, pairs, dyb, cout, wt, dxa, ca, dxb, cb):
+    """(dxa, dxb) = the two column blocks of the input gradient, one gather pass over dyb
+    (pcs_sparse_conv_cat_dgrad, pcs_sparse_conv_cat_dgrad_pairs); wt = _weight_t(wb)."""
+    (rows, taps), st = nmap.shape, L.stream_ptr(dyb.device)
+    if pairs is None:
+        L.call("pcs_sparse_conv_cat_dgrad", L.ptr(nmap), rows, taps, L.ptr(dyb), cout, L.ptr(wt), L.ptr(dxa), ca,
+               L.ptr(dxb), cb, L.BF16, 1, st)
+        return
+    pin, _, ppos, tap_off, P = pairs
+    z = torch.empty(max(P, 1), ca + cb, dtype=torch.float32, device=dyb.device)
+    L.call("pcs_sparse_conv_cat_dgrad_pairs", L.ptr(pin), L.ptr(ppos), ct.addressof(tap_off), taps, rows, L.ptr(dyb), cout,
+           L.ptr(wt), L.ptr(z), L.ptr(dxa), ca, L.ptr(dxb), cb, L.BF16, 1, st)
+
+
+def _sparse_wgrad_cat(nmap, pairs_fn, xa, xb, dyb, has_bias, use_pairs):
+    """_sparse_wgrad with X's columns taken from xa, then xb; the workspaces are the concatenated
+    layer's (the same split geometry, so the same summation order)."""
+    (rows, taps), ca, cb, cout = nmap.shape, xa.shape[1], xb.shape[1], dyb.shape[1]
+    cin = ca + cb
+    if use_pairs:
+        pin, pout, _, tap_off, _ = pairs_fn()
+        nbytes = L.workspace("pcs_sparse_conv_wgrad_pairs_workspace", ct.addressof(tap_off), taps, rows, cin, cout)
+        name, head = "pcs_sparse_conv_cat_wgrad_pairs", (L.ptr(pin), L.ptr(pout), ct.addressof(tap_off), taps, rows)
+    else:
+        nbytes = L.workspace("pcs_sparse_conv_wgrad_workspace", rows, taps, cin, cout)
+        name, head = "pcs_sparse_conv_cat_wgrad", (L.ptr(nmap), rows, taps)
+    head += (L.ptr(xa), ca, L.ptr(xb), cb, L.ptr(dyb), cout)
+    return _wgrad(name, head, nbytes, taps, cin, cout, cin, cout, has_bias, xa.device)
+
+
+class _SubMConvCatFn(torch.autograd.Function):
+    """_SubMConvFn on x = [xa | xb] (ca, cb and cout multiples of 64), which is never built: the
+    kernels read the two arrays, autograd keeps xa and xb themselves, and one gather pass over dy
+    writes both input gradients.  The dispatch is _SubMConvFn's at ca + cb input channels."""
+
+    @staticmethod
+    def forward(ctx, xa, xb, wk, bias, sv, out_dtype):
+        nbr = sv.nbr
+        V, ca, cb, cout = xa.shape[0], xa.shape[1], xb.shape[1], wk.shape[0]
+        xa, xb = xa.contiguous(), xb.contiguous()
+        wb = _bf16_2d(wk, cout, TAPS * (ca + cb))
+        bk = None if bias is None else bias.float().contiguous()
+        y = torch.empty(V, cout, dtype=out_dtype, device=xa.device)
+        pairs = sv.use_pairs()
+        if V > 0:
+            _conv_taps_cat(nbr, sv.pairs() if pairs else None, xa, ca, xb, cb, wb, cout, bk, y,
+                           L.BF16 if out_dtype == torch.bfloat16 else L.F32)
+        ctx.save_for_backward(xa, xb, wb, nbr)
+        ctx.sv, ctx.pairs = sv, pairs
+        ctx.wpairs = PAIR_WGRAD and V > 0 and (ca + cb) * cout <= PAIR_WGRAD_MAX_CH2
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xa, xb, wb, nbr = ctx.saved_tensors
+        (V, ca), cb, cout, dev = xa.shape, xb.shape[1], wb.shape[0], xa.device
+        need_a, need_b, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        need_w = need_w or (ctx.has_bias and ctx.needs_input_grad[3])
+        dxa = torch.empty(V, ca, dtype=torch.bfloat16, device=dev) if need_a else None
+        dxb = torch.empty(V, cb, dtype=torch.bfloat16, device=dev) if need_b else None
+        dwk = db = None
+        if V == 0:   # an empty level: the entry points launch nothing and write nothing
+            if need_w:
+                dwk = torch.zeros(cout, TAPS * (ca + cb), dtype=torch.float32, device=dev)
+                db = torch.zeros(cout, dtype=torch.float32, device=dev) if ctx.has_bias else None
+            return dxa, dxb, dwk, db, None, None
+        dyb = _bf16_2d(dy, V, cout)
+        pairs = ctx.sv.pairs() if ctx.pairs else None
+        if need_a or need_b:
+            wt = _weight_t(wb, TAPS)   # [ca + cb, 27 * cout]: a row block per source
+            if need_a and need_b:
+                _dgrad_taps_cat(nbr, pairs, dyb, cout, wt, dxa, ca, dxb, cb)
+            elif need_a:
+                _conv_taps(nbr, pairs, dyb, cout, wt[:ca], ca, None, dxa, L.BF16, 1)
+            else:
+                _conv_taps(nbr, pairs, dyb, cout, wt[ca:], cb, None, dxb, L.BF16, 1)
+        if need_w:
+            dwk, db = _sparse_wgrad_cat(nbr, ctx.sv.pairs, xa, xb, dyb, ctx.has_bias, ctx.wpairs)
+        return dxa, dxb, dwk, db, None, None
+
+
+def submanifold_conv3d_cat(xa, xb, weight, sv: SparseVoxels, bias=None, out_dtype=torch.bfloat16):
+    """submanifold_conv3d(torch.cat([xa, xb], 1), weight, sv, bias, out_dtype) without the
+    concatenated tensor, and bit-identical to it (the same k-step and summation order): xa bf16
+    [V, CA], xb bf16 [V, CB], weight [Cout, CA + CB, 3, 3, 3] (the concatenated layer's, fp32), bias
+    [Cout] or None.  The forward writes and autograd keeps no [V, CA + CB] tensor, and the backward
+    writes the two input gradients from one gather pass over dy (None for an input that needs none).
+    The two-source kernels take CA, CB and Cout in multiples of 64; any other width runs torch.cat
+    and submanifold_conv3d (zero-padded there): those shapes have no two-source path."""
+    if not (xa.is_cuda and xb.is_cuda):
+        raise RuntimeError("pcs_amd sparse conv runs on a HIP device only (no CPU fallback)")
+    V = sv.nbr.shape[0]
+    for name, t in (("xa", xa), ("xb", xb)):
+        if t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape[0] != V:
+            raise ValueError(f"{name} must be bf16 [{V}, C]: one row per voxel of the [V, 27] neighbour map")
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("out_dtype must be torch.bfloat16 or torch.float32")
+    ca, cb, cout = xa.shape[1], xb.shape[1], weight.shape[0]
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+        raise ValueError("submanifold_conv3d_cat is the 3x3x3 form")
+    if weight.shape[1] != ca + cb:
+        raise ValueError(f"weight has {weight.shape[1]} input channels, xa and xb have {ca} + {cb}")
+    if bias is not None and bias.shape != (cout,):
+        raise ValueError(f"bias must be [{cout}]")
+    if ca % CH_ALIGN or cb % CH_ALIGN or cout % CH_ALIGN or ca == 0 or cb == 0:
+        return submanifold_conv3d(torch.cat([xa, xb], 1), weight, sv, bias, out_dtype)
+    wk = weight.permute(0, 2, 3, 4, 1).reshape(cout, TAPS * (ca + cb))
+    return _SubMConvCatFn.apply(xa, xb, wk, bias, sv, out_dtype)
+
+
+class SubMConv3dCat(torch.nn.Module):
+    """SubMConv3d(ca + cb, cout) applied to the channel concatenation of two inputs without building
+    it (submanifold_conv3d_cat): a U-Net decoder's convolution of (up, skip).  The parameters are
+    exactly nn.Conv3d(ca + cb, cout, 3, padding=1)'s, so state dicts load into SubMConv3d(ca + cb,
+    cout) and back.  Widths off the multiple of 64 run torch.cat and the single-source layer."""
+
+    def __init__(self, ca, cb, cout, bias=True):
+        super().__init__()
+        ref = torch.nn.Conv3d(ca + cb, cout, 3, 1, 1, bias=bias)
+        self.weight, self.bias = ref.weight, ref.bias
+        self.ca, self.cb = ca, cb
+
+    def forward(self, xa, xb, sv: SparseVoxels, out_dtype=torch.bfloat16):
+        if xa.shape[-1] != self.ca or xb.shape[-1] != self.cb:
+            raise ValueError(f"SubMConv3dCat({self.ca}, {self.cb}): got {xa.shape[-1]} and {xb.shape[-1]} channels")
+        return submanifold_conv3d_cat(xa, xb, self.weight, sv, self.bias, out_dtype)
+
+
 # ---- stride-2 down / up convolutions (k = 2, s = 2) between a fine level and its coarse level
 K2_TAPS = 8
 
@@ -406,6 +558,6 @@ class SparseUpConv3d(torch.nn.Module):
         return sparse_conv_transpose3d_up(x, self.weight, link, self.bias, out_dtype)
 
 
-__all__ = ["CH_ALIGN", "CoarseLink", "SparseDownConv3d", "SparseUpConv3d", "SparseVoxels", "SubMConv3d", "coarsen",
-           "sparse_conv3d_down", "sparse_conv_transpose3d_up", "sparse_from_keys", "sparse_voxels",
-           "submanifold_conv3d"]
+__all__ = ["CH_ALIGN", "CoarseLink", "SparseDownConv3d", "SparseUpConv3d", "SparseVoxels", "SubMConv3d", "SubMConv3dCat",
+           "coarsen", "sparse_conv3d_down", "sparse_conv_transpose3d_up", "sparse_from_keys", "sparse_voxels",
+           "submanifold_conv3d", "submanifold_conv3d_cat"]
