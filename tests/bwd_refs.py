@@ -3,7 +3,8 @@ test module): pcs_wgrad with dy_mode PCS_PRO_BWD / PCS_PRO_RAW and pcs_gemm with
 PCS_EPI_DGRAD / PCS_EPI_RAW.  tests/test_bwd_refs.py proves them against torch autograd in fp64 on
 the CPU; tests/test_gpu_bwd_unfused.py compares the kernels with them.  The case lists both files
 walk are here too, so that the CPU file can check the sensitivity of exactly the cases the GPU
-file runs.
+file runs.  x_operand and dgrad_from (the EPI_DGRAD / EPI_RAW epilogue on any staged operand, of
+which dgrad_ref is the PRO_BWD case) also serve the forward restatement, tests/fwd_refs.py.
 
 Everything is NumPy float64 on arrays shaped [B, N, C] that hold the values as stored (fp32 or
 bf16).  For bf16 the references round dy and x to bf16 (round to nearest even, straight from
@@ -78,8 +79,12 @@ def dy_operand(dZ, Y, alpha, beta, gamma, mode, dtype):
     return _stage(v, U * (np.abs(inner) + np.abs(v)), dtype)
 
 
-def x_operand(X, s, t, keep, keep_scale, mode, dtype):
-    """x = relu(X s + t) keep keep_scale (PRO_BNRELU; keep None: no dropout) or X (PRO_RAW)."""
+def x_operand(X, s, t, keep, keep_scale, mode, dtype, folded=False):
+    """x = relu(X s + t) keep keep_scale (PRO_BNRELU; keep None: no dropout) or X (PRO_RAW).
+    folded: the kernel multiplies s and t by keep_scale first (the streaming forward kernel), which
+    rounds each of them once before the fma: U keep_scale (|X s| + |t|) + U |x| where the ReLU is
+    open (the data keep X s + t exactly 0, with X = t = 0, or ZGAP away from it, so it opens for
+    the same elements)."""
     X = f64(X)
     if mode == PRO_RAW:
         return dict(v=X, err=np.zeros_like(X), flag=np.zeros(X.shape, bool))
@@ -87,8 +92,12 @@ def x_operand(X, s, t, keep, keep_scale, mode, dtype):
     x = np.maximum(X * f64(s) + f64(t), 0.0)
     err = U * x
     if keep is not None:
-        x = x * np.asarray(keep, bool) * float(keep_scale)
-        err = 2.0 * U * x
+        k = np.asarray(keep, bool) * float(keep_scale)
+        if folded:
+            err = U * (x > 0) * k * (np.abs(X * f64(s)) + np.abs(f64(t))) + U * x * k
+        x = x * k
+        if not folded:
+            err = 2.0 * U * x
     return _stage(x, err, dtype)
 
 
@@ -119,13 +128,22 @@ def wgrad_ref(dZ, Y, alpha, beta, gamma, X, s, t, keep, keep_scale, dy_mode, x_m
 # ---------------------------------------------------------------------------------------
 def dgrad_ref(dZ, Y, alpha, beta, gamma, W, addend, Yp, es, et, keep, keep_scale, mean, rstd, dtype,
               ge=False, row_weight=None):
-    """v = dy W^T (+ addend), dz = (es Yp + et > 0 ? v keep keep_scale : 0) (es = et = None: Yp > 0;
-    keep None: no dropout), per-scene S1 = sum dz and S2 = sum dz (Yp - mean) rstd (0 when rstd is
-    None), and raw = dy W^T (the PCS_EPI_RAW output).  W [Ncols, K]; the rest [B, N, C].  ge turns
-    the mask into >= 0 and row_weight [B, N] weighs the rows of S1 / S2 (perturbed references of
-    the sensitivity tests only).  Returns the values, their bounds as e_<name>, zmin = the smallest
-    non-zero |es Yp + et| and the share of flagged dy elements."""
-    dy = dy_operand(dZ, Y, alpha, beta, gamma, PRO_BWD, dtype)
+    """The PCS_PRO_BWD input gradient: dgrad_from on dy = alpha dZ + beta + gamma Y as staged."""
+    return dgrad_from(dy_operand(dZ, Y, alpha, beta, gamma, PRO_BWD, dtype), W, addend, Yp, es, et, keep,
+                      keep_scale, mean, rstd, dtype, ge=ge, row_weight=row_weight)
+
+
+def dgrad_from(dy, W, addend, Yp, es, et, keep, keep_scale, mean, rstd, dtype, bias=None, ge=False,
+               row_weight=None):
+    """The PCS_EPI_DGRAD / PCS_EPI_RAW epilogue on a staged operand dy (the v / err / flag dict of
+    dy_operand or x_operand): v = dy W^T (+ bias) (+ addend), dz = (es Yp + et > 0 ? v keep keep_scale
+    : 0) (es = et = None: Yp > 0; keep None: no dropout), per-scene S1 = sum dz and
+    S2 = sum dz (Yp - mean) rstd (0 when rstd is None), and raw = dy W^T (the PCS_EPI_RAW output).
+    W [Ncols, K], bias [Ncols]; the rest [B, N, C].  The bias joins the accumulator before it is
+    rounded to the storage dtype (one more fp32 add).  ge turns the mask into >= 0 and row_weight
+    [B, N] weighs the rows of S1 / S2 (perturbed references of the sensitivity tests only).  Returns
+    the values, their bounds as e_<name>, zmin = the smallest non-zero |es Yp + et| and the share
+    of flagged dy elements."""
     W = f64(W)
     bf = dtype != "f32"
     acc = dy["v"] @ W.T
@@ -135,6 +153,10 @@ def dgrad_ref(dZ, Y, alpha, beta, gamma, W, addend, Yp, es, et, keep, keep_scale
     if Yp is None:
         return out
     Yp = f64(Yp)
+    if bias is not None:
+        acc = acc + f64(bias)
+        e_acc = e_acc + U * np.abs(acc) * SLACK
+        r_acc = BF16_U * (np.abs(acc) + e_acc) if bf else 0.0
     v, e_v = acc, e_acc + r_acc
     if addend is not None:
         v = acc + f64(addend)
