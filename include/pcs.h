@@ -899,6 +899,61 @@ int pcs_sparse_bn_bwd_apply(const void *DZ, int32_t ydtype, const void *X, int32
                             const float *beta_c, const float *gamma_c, int64_t V, int32_t C, void *dX,
                             pcs_stream_t stream);
 
+/*
+ * The per-point ends of the occupied-voxel U-Net (csrc/pointhead.hip; build-defined, the numpy
+ * statement is tests/point_head_refs.py): the lift relu(Linear(point)) -> voxel mean and the head
+ * trilinear devoxelize -> Linear (-> weighted cross-entropy), forward and backward, without a [T, C]
+ * array in either direction.  C % 8 == 0, 8 <= C <= 1024; 1 <= Cin <= 8; 1 <= K <= 16; fp32
+ * arithmetic, no atomics, fixed summation order (reductions over rows: per-block partials of at most
+ * 2048 non-empty blocks, then pcs_reduce_partials).  order / seg_off / inv_count are
+ * PointVoxelMap.points_by_voxel()'s arrays, pair_point / pair_weight / seg_off pairs_by_voxel()'s,
+ * corner / weight the map's own (16-byte aligned); every index array lives on the DEVICE.
+ * pcs_point_lift_mean: Y[v][c] = inv_count[v] * sum_{j in [seg_off[v], seg_off[v + 1])} relu(z[j][c]),
+ *   z[j][c] = bias[c] + sum_{i < Cin} W[c][i] * P[order[j]][i], ascending j; P f32 [T, ldp], ldp >= Cin;
+ *   W f32 [C, Cin]; bias f32 [C] or NULL (= 0); Y [V, C] PCS_BF16 or PCS_F32.  An empty segment
+ *   stores a zero row; order[j] < 0 is skipped.
+ * pcs_point_lift_mean_bwd: g[j][c] = z[j][c] > 0 ? dV[v][c] * inv_count[v] : 0 with z recomputed by
+ *   the forward's expression; dW[c][i] = sum_j g[j][c] * P[order[j]][i]; db[c] = sum_j g[j][c] (db
+ *   NULL: skipped).  dV [V, C] in dvdtype.  The points get no gradient.  workspace: 16-byte aligned,
+ *   at least pcs_point_lift_bwd_workspace(V, C, Cin) bytes.
+ * pcs_point_head_project: Z[v][k] = sum_c X[v][c] * W[k][c]; X [V, C] in xdtype, W f32 [K, C], Z f32
+ *   [V, K].
+ * pcs_point_head_logits: one thread per point, l[k] = bias[k] + sum_{j < 8} weight[p][j] *
+ *   Z[corner[p][j]][k] (corner -1 skipped, bias NULL = 0).  labels NULL: logits [T, K] (required) is
+ *   stored, nothing else.  Otherwise labels i64 [T], class_weight f32 [K], inv_wsum a device scalar
+ *   (pcs_ce_weight_sum's out[2]); for y = labels[p] in [0, K): nll = logsumexp(l) - l[y];
+ *   loss[0] = inv_wsum * sum_p cw[y] * nll; dlogits[p][k] = cw[y] * inv_wsum * (softmax(l)[k] -
+ *   [k == y]); db[k] = sum_p dlogits[p][k].  Any other label (-1 = ignored) contributes nothing,
+ *   gets a zero dlogits row and reads nothing through its value.  Without a valid label inv_wsum is
+ *   0 and loss[0] NaN (torch's 0 / 0), dlogits and db zero.  logits, dlogits and db may each be NULL (skipped).  workspace (with
+ *   labels): 16-byte aligned, at least pcs_point_head_workspace(T, V, C, K) bytes, the size that
+ *   serves this call and pcs_point_head_bwd.
+ * pcs_point_head_bwd: dZ[v][k] = g * sum_j pair_weight[j] * dlogits[pair_point[j]][k] over v's
+ *   segment, ascending j, g = *gscale (device scalar; NULL = 1), held as f32 [V, K] in the
+ *   workspace; dX[v][c] = sum_k dZ[v][k] * W[k][c] in xdtype (NULL: skipped); dW[k][c] = sum_v
+ *   dZ[v][k] * X[v][c] (NULL: skipped).
+ * Every output row is stored exactly once; V == 0 / T == 0 return 0 without a launch.
+ */
+int pcs_point_lift_mean(const float *P, int64_t ldp, int32_t Cin, const float *W, const float *bias,
+                        const int32_t *order, const int64_t *seg_off, const float *inv_count, int64_t V, int32_t C,
+                        void *Y, int32_t ydtype, pcs_stream_t stream);
+int64_t pcs_point_lift_bwd_workspace(int64_t V, int32_t C, int32_t Cin);
+int pcs_point_lift_mean_bwd(const void *dV, int32_t dvdtype, const float *P, int64_t ldp, int32_t Cin, const float *W,
+                            const float *bias, const int32_t *order, const int64_t *seg_off, const float *inv_count,
+                            int64_t V, int32_t C, void *workspace, int64_t workspace_bytes, float *dW, float *db,
+                            pcs_stream_t stream);
+int pcs_point_head_project(const void *X, int32_t xdtype, int64_t V, int32_t C, const float *W, int32_t K, float *Z,
+                           pcs_stream_t stream);
+int64_t pcs_point_head_workspace(int64_t T, int64_t V, int32_t C, int32_t K);
+int pcs_point_head_logits(const float *Z, const int32_t *corner, const float *weight, int64_t T, int32_t K,
+                          const float *bias, const int64_t *labels, const float *class_weight, const float *inv_wsum,
+                          float *logits, float *dlogits, void *workspace, int64_t workspace_bytes, float *loss,
+                          float *db, pcs_stream_t stream);
+int pcs_point_head_bwd(const float *dlogits, const int32_t *pair_point, const float *pair_weight,
+                       const int64_t *seg_off, const void *X, int32_t xdtype, int64_t V, int32_t C, const float *W,
+                       int32_t K, const float *gscale, void *dX, void *workspace, int64_t workspace_bytes, float *dW,
+                       pcs_stream_t stream);
+
 /* Build-time identification and error string. pcs_abi_version() returns PCS_ABI_VERSION,
  * bumped with every change to an argument struct's layout or an entry point's signature
  * (2: pcs_gemm_args gained `gram`, the w4 entry points were removed; 3: prologue 3, three

@@ -32,6 +32,9 @@ _LAZY = {
     "point_voxel_map": ("pointvoxel", "point_voxel_map"),
     "voxel_mean": ("pointvoxel", "voxel_mean"),
     "devoxelize": ("pointvoxel", "devoxelize"),
+    "point_lift_mean": ("pointhead", "point_lift_mean"),
+    "point_head": ("pointhead", "point_head"),
+    "point_head_loss": ("pointhead", "point_head_loss"),
     "sparse_batch_norm": ("sparse_norm", "sparse_batch_norm"),
     "SparseBatchNorm": ("sparse_norm", "SparseBatchNorm"),
     "SparseResBlock": ("sparse_norm", "SparseResBlock"),

@@ -180,6 +180,16 @@ SIGNATURES = [
     ("pcs_sparse_bn_bwd_reduce", ct.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _vp,
                                             _vp, _vp]),
     ("pcs_sparse_bn_bwd_apply", ct.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    ("pcs_point_lift_mean", ct.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp]),
+    ("pcs_point_lift_bwd_workspace", _i64, [_i64, _i32, _i32]),
+    ("pcs_point_lift_mean_bwd", ct.c_int, [_vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64,
+                                           _vp, _vp, _vp]),
+    ("pcs_point_head_project", ct.c_int, [_vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp]),
+    ("pcs_point_head_workspace", _i64, [_i64, _i64, _i32, _i32]),
+    ("pcs_point_head_logits", ct.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                         _vp]),
+    ("pcs_point_head_bwd", ct.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp,
+                                      _vp]),
     ("pcs_gram_workspace", _i64, [_i64, _i64, _i32, _i32, ct.POINTER(_i32)]),
     ("pcs_gram", ct.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     ("pcs_pool_rows_add", ct.c_int, [_vp, _i32, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32,

@@ -9,8 +9,10 @@ the voxel vocabulary: the reference has no voxel grid.
     loss = F.cross_entropy(logits, rb.labels.cuda(), weight=class_weight, ignore_index=-1)
 
 Every convolution is a HIP kernel on occupied voxels only; the decoder's skip connection is the
-two-source layer (sparse.SubMConv3dCat), so no level builds a concatenated tensor.  The loss stays
-the caller's.  BatchNorm statistics are per device.  The model is a plain nn.Module: FusedAdam
+two-source layer (sparse.SubMConv3dCat), so no level builds a concatenated tensor.  model(rb) leaves
+the loss to the caller; model(rb, fused=True) and model.loss(rb, class_weight) run the two per-point
+ends through pcs_amd.pointhead (the lift recomputed inside the voxel mean, the head projected before
+it is interpolated, the cross-entropy where the logits are).  BatchNorm statistics are per device.  The model is a plain nn.Module: FusedAdam
 (optim.flatten_parameters is generic) works on it; checkpoint.save_checkpoint / load_checkpoint
 rebuild a PointNetSegmentation and do not apply, use state_dict() / load_state_dict().
 """
@@ -21,6 +23,7 @@ from dataclasses import dataclass
 import torch
 
 from .data import RaggedBatch
+from .pointhead import point_head, point_head_loss, point_lift_mean
 from .pointvoxel import devoxelize, point_voxel_map, voxel_mean
 from .sparse import (CoarseLink, SparseDownConv3d, SparseUpConv3d, SparseVoxels, SubMConv3dCat, coarsen,
                      sparse_voxels)
@@ -115,7 +118,8 @@ class SparseUNetSegmentation(torch.nn.Module):
         self.lift = torch.nn.Linear(self.in_channels, self.unet.widths[0])
         self.head = torch.nn.Linear(self.unet.widths[0], self.num_classes)
 
-    def forward(self, rb: RaggedBatch):
+    def _levels(self, rb: RaggedBatch):
+        """(device, pyramid, point map of the finest level) of a batch."""
         dev = self.lift.weight.device
         if dev.type != "cuda":
             raise RuntimeError("pcs_amd SparseUNetSegmentation runs on a HIP device only (no CPU fallback)")
@@ -125,11 +129,31 @@ class SparseUNetSegmentation(torch.nn.Module):
         vb = voxelize(rb, self.grid, self.lo, self.hi, max(self.num_classes, 1), device=dev)
         sv = sparse_voxels(rb, vb, self.lo, self.hi)
         pyr = sparse_pyramid(sv, self.unet.depth)
-        pvm = point_voxel_map(rb, sv, self.lo, self.hi)
+        return dev, pyr, point_voxel_map(rb, sv, self.lo, self.hi)
+
+    def _fused_features(self, rb, dev, pyr, pvm):
+        """The U-Net's output on the finest level with the lift fused into the voxel mean."""
+        x = point_lift_mean(rb.points.to(dev, torch.float32), self.lift.weight, self.lift.bias, pvm)
+        return self.unet(x, pyr)
+
+    def forward(self, rb: RaggedBatch, fused: bool = False):
+        """fused=True: the same function through pointhead.point_lift_mean and point_head on the same
+        lift / head parameters (no [T, w_0] array in either direction; another summation order)."""
+        dev, pyr, pvm = self._levels(rb)
+        if fused:
+            return point_head(self._fused_features(rb, dev, pyr, pvm), pvm, self.head.weight, self.head.bias)
         pts = rb.points.to(dev, torch.float32)[:, :self.in_channels]
         x = voxel_mean(torch.relu(self.lift(pts)), pvm)
         x = self.unet(x, pyr)
         return self.head(devoxelize(x, pvm))
+
+    def loss(self, rb: RaggedBatch, class_weight=None, return_logits: bool = False):
+        """The weighted cross-entropy of the batch's own labels (-1 = ignored) on the fused path:
+        F.cross_entropy(self(rb), rb.labels, weight=class_weight, ignore_index=-1) as a 0-dim fp32
+        tensor, or (loss, logits.detach()) with return_logits (pointhead.point_head_loss)."""
+        dev, pyr, pvm = self._levels(rb)
+        x = self._fused_features(rb, dev, pyr, pvm)
+        return point_head_loss(x, pvm, self.head.weight, self.head.bias, rb.labels.to(dev), class_weight, return_logits)
 
 
 __all__ = ["SparsePyramid", "SparseUNet", "SparseUNetSegmentation", "sparse_pyramid"]
