@@ -12,71 +12,22 @@
 //   bwd      dZ[v] = g * the sum of weight * dlogits over v's (point, corner) pairs (fp32 [V, K], the
 //            only per-voxel array of the backward), then dX = dZ W and the partials of dW = dZ^T X
 //
-// All are bandwidth-bound (no MFMA; LDS only for the block reductions): a row of C channels is
-// C / 8 lanes of 8 elements, a workgroup of 256 threads holds 256 / (C / 8) rows per pass (the lanes
-// left over idle).  Arithmetic is fp32.  Nothing is added atomically, every output row is stored
-// once, and every sum runs in a fixed order (per-thread ascending, then a fixed block order, then
-// pcs_reduce_partials over at most 2048 non-empty blocks): results are bitwise reproducible.
-#include "common.h"
+// All are bandwidth-bound (no MFMA; LDS only for the block reductions) over the lanes-of-E-elements
+// row scheme of row_piece.h, with E = 8 for either dtype.  Arithmetic is fp32.  Nothing is added
+// atomically, every output row is stored once, and every sum runs in a fixed order (per-thread
+// ascending, then a fixed block order, then pcs_reduce_partials over at most 2048 non-empty
+// blocks): results are bitwise reproducible.
+#include "row_piece.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int E = 8;               // channels of a lane
-constexpr int MAX_C = 1024;
+using namespace pcs_rows;
+
+constexpr int E = 8;            // channels of a lane
 constexpr int MAX_CIN = 8;
 constexpr int MAX_K = 16;
 constexpr int CORNERS = 8;
-constexpr int ROW_TILE = 64;       // rows per block of a reduction are a multiple of this
-constexpr int MAX_BLOCKS = 2048;   // of a reduction (~8 per CU)
-constexpr int SEG_UNROLL = 4;      // entries of a segment a lane keeps in flight
-
-// a lane's 8 elements of a row as raw 16-byte registers: loads first, conversion at the use
-template <typename T>
-struct Raw {
-  static constexpr int NQ = E * Elem<T>::SIZE / 16;
-  u32x4 q[NQ];
-};
-
-template <typename T>
-PCS_DEV void raw_load(Raw<T> &r, const T *__restrict__ p, bool present) {
-#pragma unroll
-  for (int i = 0; i < Raw<T>::NQ; ++i)
-    r.q[i] = present ? reinterpret_cast<const u32x4 *>(p)[i] : mk_u32x4(0u, 0u, 0u, 0u);
-}
-
-template <typename T>
-PCS_DEV void raw_unpack(const Raw<T> &r, float (&v)[E]) {
-  constexpr int EPC = Elem<T>::EPC;
-#pragma unroll
-  for (int i = 0; i < Raw<T>::NQ; ++i) {
-    float t[EPC];
-    unpack_chunk(r.q[i], t);
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) v[i * EPC + e] = t[e];
-  }
-}
-
-template <typename T>
-PCS_DEV void store_piece(T *__restrict__ p, const float (&v)[E]) {
-  constexpr int EPC = Elem<T>::EPC;
-#pragma unroll
-  for (int i = 0; i < E / EPC; ++i) {
-    float t[EPC];
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) t[e] = v[i * EPC + e];
-    reinterpret_cast<u32x4 *>(p)[i] = pack_chunk(t);
-  }
-}
-
-// this thread's (row slot r0, piece cc) in a workgroup of rpp = 256 / lpr rows (lpr <= 128); false:
-// a lane left over
-PCS_DEV bool lane_slot(int lpr, int &rpp, int &r0, int &cc) {
-  rpp = THREADS / lpr;
-  r0 = (int)threadIdx.x / lpr;
-  cc = (int)threadIdx.x - r0 * lpr;
-  return r0 < rpp;
-}
+constexpr int SEG_UNROLL = 4;   // entries of a segment a lane keeps in flight
 
 // sm[e][slot * lpr + piece] holds one value per lane: column c = piece * 8 + e summed over the row
 // slots in slot order
@@ -150,7 +101,7 @@ __global__ __launch_bounds__(THREADS) void lift_mean_kernel(const float *__restr
     const float sc = inv_count[v];
 #pragma unroll
     for (int e = 0; e < E; ++e) acc[e] *= sc;
-    store_piece<YT>(Y + v * C + c0, acc);
+    store_piece<YT, E>(Y + v * C + c0, acc);
   }
 }
 
@@ -181,12 +132,12 @@ __global__ __launch_bounds__(THREADS) void lift_bwd_kernel(const DT *__restrict_
     float w[E][CIN], b[E];
     load_lift_weights<CIN>(W, bias, c0, w, b);
     for (int64_t v = lo + r0; v < hi; v += rpp) {
-      Raw<DT> rd;
-      raw_load<DT>(rd, dV + v * C + c0, true);
+      Raw<DT, E> rd;
+      raw_load<DT, E>(rd, dV + v * C + c0, true);
       const int64_t j0 = seg_off[v], j1 = seg_off[v + 1];
       const float sc = inv_count[v];
       float d[E];
-      raw_unpack<DT>(rd, d);
+      raw_unpack<DT, E>(rd, d);
 #pragma unroll
       for (int e = 0; e < E; ++e) d[e] *= sc;
       for (int64_t j = j0; j < j1; j += SEG_UNROLL) {
@@ -262,16 +213,16 @@ __global__ __launch_bounds__(THREADS) void head_project_kernel(const XT *__restr
   const int64_t step = (int64_t)rpp * U;
   const int per_u = rpp * KT;
   for (int64_t base = (int64_t)blockIdx.x * step; base < V; base += (int64_t)gridDim.x * step) {
-    Raw<XT> rx[U];
+    Raw<XT, E> rx[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int64_t row = base + (int64_t)u * rpp + r0;
-      raw_load<XT>(rx[u], X + row * C + c0, active && row < V);
+      raw_load<XT, E>(rx[u], X + row * C + c0, active && row < V);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       float x[E];
-      raw_unpack<XT>(rx[u], x);
+      raw_unpack<XT, E>(rx[u], x);
 #pragma unroll
       for (int k = 0; k < KT; ++k) {
         float s = 0.f;
@@ -456,13 +407,13 @@ __global__ __launch_bounds__(THREADS) void head_bwd_kernel(const float *__restri
     float w[KT][E];
     load_head_weights<KT>(W, dX ? K : 0, C, c0, w);
     for (int64_t v = lo + r0; v < hi; v += (int64_t)rpp * U) {
-      Raw<XT> rx[U];
+      Raw<XT, E> rx[U];
       float dz[U][KT];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t row = v + (int64_t)u * rpp;
         const bool in = row < hi;
-        raw_load<XT>(rx[u], X + row * C + c0, in && part != nullptr);
+        raw_load<XT, E>(rx[u], X + row * C + c0, in && part != nullptr);
 #pragma unroll
         for (int k = 0; k < KT; ++k) dz[u][k] = (in && k < K) ? dZ[row * K + k] : 0.f;
       }
@@ -472,7 +423,7 @@ __global__ __launch_bounds__(THREADS) void head_bwd_kernel(const float *__restri
         if (row < hi) {
           if (part) {
             float x[E];
-            raw_unpack<XT>(rx[u], x);
+            raw_unpack<XT, E>(rx[u], x);
 #pragma unroll
             for (int k = 0; k < KT; ++k) {
 #pragma unroll
@@ -488,7 +439,7 @@ __global__ __launch_bounds__(THREADS) void head_bwd_kernel(const float *__restri
 #pragma unroll
               for (int e = 0; e < E; ++e) o[e] = fmaf(dz[u][k], w[k][e], o[e]);
             }
-            store_piece<XT>(dX + row * C + c0, o);
+            store_piece<XT, E>(dX + row * C + c0, o);
           }
         }
       }
@@ -508,25 +459,11 @@ __global__ __launch_bounds__(THREADS) void head_bwd_kernel(const float *__restri
 }
 
 // ---- host side
-struct Blocks {
-  int64_t per;   // rows (points) of a block, a multiple of tile
-  int32_t n;     // blocks: they tile [0, total) and none is empty
-};
-
-Blocks reduction_blocks(int64_t total, int64_t tile) {
-  const int64_t span = tile * MAX_BLOCKS;
-  Blocks b;
-  b.per = tile * pcs_max64((total + span - 1) / span, 1);
-  b.n = (int32_t)((total + b.per - 1) / b.per);
-  return b;
-}
-
 int stream_blocks(int64_t rows, int64_t rows_per_block, int64_t cap) {
   const int64_t b = (rows + rows_per_block - 1) / rows_per_block;
   return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
-bool known(int32_t dtype) { return dtype == PCS_F32 || dtype == PCS_BF16; }
 bool bad_channels(int32_t C) { return C < E || C % E != 0 || C > MAX_C; }
 bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 int64_t round4(int64_t n) { return (n + 3) / 4 * 4; }

@@ -4,36 +4,29 @@
 // Build-defined like the rest of the voxel vocabulary: the numpy statement is
 // tests/point_voxel_refs.py.
 //
-//   u_d      ((p_d - lo_d) / (hi_d - lo_d)) * G, float32, the expression of voxel_of (sparse.hip)
+//   u_d      ((p_d - lo_d) / (hi_d - lo_d)) * G, float32, the expression of voxel_of (voxel_geom.h)
 //   own      row of the voxel clamp(floor(u), 0, G - 1), or -1 when the level does not hold it
 //   corners  c_d = min(max(u_d, 0), G) - 0.5, b_d = floor(c_d), f_d = c_d - b_d; corner k =
 //            (ax * 2 + ay) * 2 + az is the voxel b + a (-1: outside the grid or unoccupied) with
 //            raw weight prod_d (a_d ? f_d : 1 - f_d), divided by the sum over the present corners
 //
-// Both row kernels are bandwidth-bound gathers (no MFMA, no LDS): a row of C channels is C / E
-// lanes of 16-byte accesses (E = 8 elements when either side is bf16, else 4), a workgroup holds
-// 256 / (C / E) rows, and every lane keeps several row loads in flight before it accumulates in
-// fp32.  Each output row is stored once (a zero row when nothing contributes), nothing is added
-// atomically, and every sum runs in a fixed order: results are bitwise reproducible.
-#include "common.h"
+// Both row kernels are bandwidth-bound gathers (no MFMA, no LDS) over the lanes-of-E-elements row
+// scheme of row_piece.h, for any C (lane_slot_wide), and every lane keeps several row loads in
+// flight before it accumulates in fp32.  Each output row is stored once (a zero row when nothing
+// contributes), nothing is added atomically, and every sum runs in a fixed order: results are
+// bitwise reproducible.
+#include "row_piece.h"
+#include "voxel_geom.h"
 #include "voxel_hash.h"
 
 namespace {
 
+using namespace pcs_rows;
+using pcs_geom::Box;
 using pcs_hash::hash_find;
 
-constexpr int THREADS = 256;
 constexpr int MAX_K = 8;
 constexpr int SEG_UNROLL = 4;   // row loads a lane keeps in flight along a segment
-
-struct Box {
-  float lo[3], hi[3];
-};
-
-int blocks_for_n(int64_t n) {
-  const int64_t b = (n + THREADS - 1) / THREADS;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
 
 // one thread per point
 __global__ __launch_bounds__(THREADS) void trilinear_index_kernel(
@@ -88,59 +81,6 @@ __global__ __launch_bounds__(THREADS) void trilinear_index_kernel(
   }
 }
 
-// ---- a lane's E-element piece of a row: raw 16-byte registers between the load and the use, so
-// that a lane issues all its loads before it waits for the first
-template <typename XT, int E>
-struct RawRow {
-  static constexpr int NQ = E * Elem<XT>::SIZE / 16;
-  u32x4 q[NQ];
-};
-
-template <typename XT, int E>
-PCS_DEV void raw_load(RawRow<XT, E> &r, const XT *__restrict__ p, bool present) {
-#pragma unroll
-  for (int i = 0; i < RawRow<XT, E>::NQ; ++i)
-    r.q[i] = present ? reinterpret_cast<const u32x4 *>(p)[i] : mk_u32x4(0u, 0u, 0u, 0u);
-}
-
-template <typename XT, int E>
-PCS_DEV void raw_fma(const RawRow<XT, E> &r, float w, float (&acc)[E]) {
-  constexpr int EPC = Elem<XT>::EPC;
-#pragma unroll
-  for (int i = 0; i < RawRow<XT, E>::NQ; ++i) {
-    float v[EPC];
-    unpack_chunk(r.q[i], v);
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) acc[i * EPC + e] += w * v[e];
-  }
-}
-
-template <typename YT, int E>
-PCS_DEV void store_piece(YT *__restrict__ p, const float (&acc)[E]) {
-  constexpr int EPC = Elem<YT>::EPC;
-#pragma unroll
-  for (int i = 0; i < E / EPC; ++i) {
-    float v[EPC];
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) v[e] = acc[i * EPC + e];
-    reinterpret_cast<u32x4 *>(p)[i] = pack_chunk(v);
-  }
-}
-
-template <typename XT, typename YT>
-struct Piece {
-  static constexpr int E = (Elem<XT>::EPC == 8 || Elem<YT>::EPC == 8) ? 8 : 4;
-};
-
-// the (row slot, first piece) of this thread in a workgroup of 256 / lpr rows (one row, pieces
-// strided by 256, when a row has more than 256 pieces); false for the lanes left over
-PCS_DEV bool lane_slot(int lpr, int &rows_per_block, int &r, int &c0) {
-  rows_per_block = lpr >= THREADS ? 1 : THREADS / lpr;
-  r = (int)threadIdx.x / lpr;
-  c0 = (int)threadIdx.x - r * lpr;
-  return r < rows_per_block;
-}
-
 // Y[m] = sum_{k < K} w[m][k] * X[idx[m][k]] (idx < 0 skipped, w NULL = 1).  KT = K at compile
 // time, or 0 for any K <= 8 (eight predicated slots).
 template <typename XT, typename YT, int KT>
@@ -151,7 +91,7 @@ __global__ __launch_bounds__(THREADS) void rows_interp_kernel(const XT *__restri
   constexpr int SLOTS = KT ? KT : MAX_K;
   const int lpr = C / E;
   int rpb, r, c0;
-  if (!lane_slot(lpr, rpb, r, c0)) return;
+  if (!lane_slot_wide(lpr, rpb, r, c0)) return;
   const int kk = KT ? KT : K;
   for (int64_t m = (int64_t)blockIdx.x * rpb + r; m < M; m += (int64_t)gridDim.x * rpb) {
     int32_t id[SLOTS];
@@ -163,7 +103,7 @@ __global__ __launch_bounds__(THREADS) void rows_interp_kernel(const XT *__restri
       wk[k] = (in && w) ? w[m * kk + k] : 1.f;
     }
     for (int c = c0; c < lpr; c += THREADS) {
-      RawRow<XT, E> raw[SLOTS];
+      Raw<XT, E> raw[SLOTS];
 #pragma unroll
       for (int k = 0; k < SLOTS; ++k) raw_load<XT, E>(raw[k], X + (int64_t)id[k] * C + c * E, id[k] >= 0);
       float acc[E];
@@ -188,7 +128,7 @@ __global__ __launch_bounds__(THREADS) void rows_segsum_kernel(const XT *__restri
   constexpr int E = Piece<XT, YT>::E;
   const int lpr = C / E;
   int rpb, r, c0;
-  if (!lane_slot(lpr, rpb, r, c0)) return;
+  if (!lane_slot_wide(lpr, rpb, r, c0)) return;
   for (int64_t m = (int64_t)blockIdx.x * rpb + r; m < M; m += (int64_t)gridDim.x * rpb) {
     const int64_t j0 = seg_off[m], j1 = seg_off[m + 1];
     const float sc = scale ? scale[m] : 1.f;
@@ -199,7 +139,7 @@ __global__ __launch_bounds__(THREADS) void rows_segsum_kernel(const XT *__restri
       for (int64_t j = j0; j < j1; j += SEG_UNROLL) {
         int32_t id[SEG_UNROLL];
         float wj[SEG_UNROLL];
-        RawRow<XT, E> raw[SEG_UNROLL];
+        Raw<XT, E> raw[SEG_UNROLL];
 #pragma unroll
         for (int u = 0; u < SEG_UNROLL; ++u) {
           const bool in = j + u < j1;
@@ -217,15 +157,6 @@ __global__ __launch_bounds__(THREADS) void rows_segsum_kernel(const XT *__restri
       store_piece<YT, E>(Y + m * C + c * E, acc);
     }
   }
-}
-
-// C a multiple of the piece: 8 when either side is bf16, else 4
-const char *check_rows(int32_t xdtype, int32_t ydtype, int32_t C) {
-  if ((xdtype != PCS_F32 && xdtype != PCS_BF16) || (ydtype != PCS_F32 && ydtype != PCS_BF16))
-    return "unknown dtype (PCS_F32 | PCS_BF16)";
-  const int e = (xdtype == PCS_BF16 || ydtype == PCS_BF16) ? 8 : 4;
-  if (C < e || C % e != 0) return "C % 8 == 0 (bf16 on either side) or C % 4 == 0 (fp32) required";
-  return nullptr;
 }
 
 int row_blocks(int64_t M, int32_t C, int e) {
@@ -273,7 +204,7 @@ extern "C" int pcs_trilinear_index(const float *points, const int64_t *offsets, 
     return pcs_set_einval("pcs_trilinear_index", "NULL pointer");
   if (T == 0) return 0;
   const Box b = {{lo_x, lo_y, lo_z}, {hi_x, hi_y, hi_z}};
-  hipLaunchKernelGGL(trilinear_index_kernel, dim3(blocks_for_n(T)), dim3(THREADS), 0,
+  hipLaunchKernelGGL(trilinear_index_kernel, dim3(pcs_geom::blocks_1d(T)), dim3(THREADS), 0,
                      reinterpret_cast<hipStream_t>(stream), points, offsets, (int)num_scenes, T, (int)grid, b,
                      table_keys, table_vals, (uint64_t)(capacity - 1), own, corner, weight);
   PCS_CHECK_LAUNCH();
@@ -284,14 +215,13 @@ extern "C" int pcs_rows_interp(const void *X, int32_t xdtype, const int32_t *idx
                                int32_t K, int32_t C, void *Y, int32_t ydtype, pcs_stream_t stream) {
   if (M < 0) return pcs_set_einval("pcs_rows_interp", "M >= 0 required");
   if (K < 1 || K > MAX_K) return pcs_set_einval("pcs_rows_interp", "1 <= K <= 8 required");
-  if (const char *msg = check_rows(xdtype, ydtype, C)) return pcs_set_einval("pcs_rows_interp", msg);
+  if (const char *msg = check_width(xdtype, ydtype, C)) return pcs_set_einval("pcs_rows_interp", msg);
   if (M > 0 && (!X || !idx || !Y)) return pcs_set_einval("pcs_rows_interp", "NULL pointer");
   if (M == 0) return 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (xdtype == PCS_BF16 && ydtype == PCS_BF16) launch_interp<bf16_t, bf16_t>(X, idx, w, M, K, C, Y, s);
-  else if (xdtype == PCS_BF16) launch_interp<bf16_t, float>(X, idx, w, M, K, C, Y, s);
-  else if (ydtype == PCS_BF16) launch_interp<float, bf16_t>(X, idx, w, M, K, C, Y, s);
-  else launch_interp<float, float>(X, idx, w, M, K, C, Y, s);
+  for_dtype_pair(xdtype, ydtype, [&](auto x, auto y) {
+    launch_interp<decltype(x), decltype(y)>(X, idx, w, M, K, C, Y, s);
+  });
   PCS_CHECK_LAUNCH();
   return 0;
 }
@@ -300,14 +230,13 @@ extern "C" int pcs_rows_segsum(const void *X, int32_t xdtype, const int32_t *src
                                const int64_t *seg_off, const float *scale, int64_t M, int32_t C, void *Y,
                                int32_t ydtype, pcs_stream_t stream) {
   if (M < 0) return pcs_set_einval("pcs_rows_segsum", "M >= 0 required");
-  if (const char *msg = check_rows(xdtype, ydtype, C)) return pcs_set_einval("pcs_rows_segsum", msg);
+  if (const char *msg = check_width(xdtype, ydtype, C)) return pcs_set_einval("pcs_rows_segsum", msg);
   if (M > 0 && (!X || !src || !seg_off || !Y)) return pcs_set_einval("pcs_rows_segsum", "NULL pointer");
   if (M == 0) return 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (xdtype == PCS_BF16 && ydtype == PCS_BF16) launch_segsum<bf16_t, bf16_t>(X, src, w, seg_off, scale, M, C, Y, s);
-  else if (xdtype == PCS_BF16) launch_segsum<bf16_t, float>(X, src, w, seg_off, scale, M, C, Y, s);
-  else if (ydtype == PCS_BF16) launch_segsum<float, bf16_t>(X, src, w, seg_off, scale, M, C, Y, s);
-  else launch_segsum<float, float>(X, src, w, seg_off, scale, M, C, Y, s);
+  for_dtype_pair(xdtype, ydtype, [&](auto x, auto y) {
+    launch_segsum<decltype(x), decltype(y)>(X, src, w, seg_off, scale, M, C, Y, s);
+  });
   PCS_CHECK_LAUNCH();
   return 0;
 }

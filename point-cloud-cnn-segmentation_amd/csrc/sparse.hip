@@ -2,7 +2,7 @@
 // (hash-indexed gather)" (BASELINE configs[2]).  Build-defined: the reference has no
 // voxel grid, so the oracle is oracle/sparse_oracle.py (numpy, dict-based), "not reference parity".
 //
-//   key          scene * G^3 + (ix * G + iy) * G + iz, the voxel key of voxel.hip
+//   key          scene * G^3 + (ix * G + iy) * G + iz, the voxel key of voxel.hip (voxel_of, voxel_geom.h)
 //   hash table   open addressing over a power-of-two capacity (>= 2 n): slot = mix(key) & (cap-1),
 //                linear probing; keys inserted with a 64-bit compare-and-swap, the value is the
 //                voxel's row.  Keys are unique, so the final table (which slot holds which key)
@@ -14,31 +14,19 @@
 //   coarse level the occupied 2x2x2 cells of an even grid (key of the cell on the G / 2 grid) and
 //                the child / parent / up maps of a k = 2, s = 2 convolution between the levels
 #include "common.h"
+#include "voxel_geom.h"
 #include "voxel_hash.h"
 
 namespace {
 
+using pcs_geom::blocks_1d;
+using pcs_geom::Box;
+using pcs_geom::voxel_of;
 using pcs_hash::EMPTY;
 using pcs_hash::hash_find;
 using pcs_hash::mix64;
 
 constexpr int THREADS = 256;
-
-PCS_DEV int64_t voxel_of(const float *p, int G, const float *lo, const float *hi) {
-  int64_t id = 0;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {   // the expression order of voxel.hip (bit-exact ids)
-    const float t = (p[d] - lo[d]) / (hi[d] - lo[d]);
-    int i = (int)floorf(t * (float)G);
-    i = i < 0 ? 0 : (i > G - 1 ? G - 1 : i);
-    id = id * G + i;
-  }
-  return id;
-}
-
-struct Box {
-  float lo[3], hi[3];
-};
 
 // keys[voxel_of_point[p]] = key of p (every point of a voxel writes the same value)
 __global__ __launch_bounds__(THREADS) void voxel_keys_kernel(const float *__restrict__ pts,
@@ -52,7 +40,7 @@ __global__ __launch_bounds__(THREADS) void voxel_keys_kernel(const float *__rest
       const int mid = (lo + hi) >> 1;
       if (offsets[mid] <= t) lo = mid; else hi = mid;
     }
-    keys[vop[t]] = (uint64_t)lo * G3 + (uint64_t)voxel_of(pts + t * 4, G, b.lo, b.hi);
+    keys[vop[t]] = (uint64_t)lo * G3 + (uint64_t)voxel_of(pts + t * 4, G, b);
   }
 }
 
@@ -145,11 +133,6 @@ __global__ __launch_bounds__(THREADS) void coarse_maps_kernel(const int64_t *__r
   }
 }
 
-int blocks_for_n(int64_t n) {
-  const int64_t b = (n + THREADS - 1) / THREADS;
-  return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
-}
-
 }  // namespace
 
 extern "C" int pcs_voxel_keys(const float *points, const int64_t *offsets, int64_t num_scenes, int64_t T, int32_t grid,
@@ -163,7 +146,7 @@ extern "C" int pcs_voxel_keys(const float *points, const int64_t *offsets, int64
     return pcs_set_einval("pcs_voxel_keys", "key overflow (num_scenes * grid^3 >= 2^64 - 1)");
   if (T == 0) return 0;
   const Box b = {{lo_x, lo_y, lo_z}, {hi_x, hi_y, hi_z}};
-  hipLaunchKernelGGL(voxel_keys_kernel, dim3(blocks_for_n(T)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(voxel_keys_kernel, dim3(blocks_1d(T)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                      points, offsets, (int)num_scenes, T, (int)grid, b, voxel_of_point, keys);
   PCS_CHECK_LAUNCH();
   return 0;
@@ -182,9 +165,9 @@ extern "C" int pcs_voxel_hash_build(const uint64_t *keys, int64_t n, uint64_t *t
       (capacity & (capacity - 1)) != 0)
     return pcs_set_einval("pcs_voxel_hash_build", "bad arguments (capacity: a power of two >= 2 n)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(hash_clear_kernel, dim3(blocks_for_n(capacity)), dim3(THREADS), 0, s, table_keys, table_vals, capacity);
+  hipLaunchKernelGGL(hash_clear_kernel, dim3(blocks_1d(capacity)), dim3(THREADS), 0, s, table_keys, table_vals, capacity);
   if (n > 0)
-    hipLaunchKernelGGL(hash_insert_kernel, dim3(blocks_for_n(n)), dim3(THREADS), 0, s, keys, n,
+    hipLaunchKernelGGL(hash_insert_kernel, dim3(blocks_1d(n)), dim3(THREADS), 0, s, keys, n,
                        reinterpret_cast<unsigned long long *>(table_keys), table_vals, (uint64_t)(capacity - 1));
   PCS_CHECK_LAUNCH();
   return 0;
@@ -196,7 +179,7 @@ extern "C" int pcs_voxel_hash_find(const uint64_t *table_keys, const int32_t *ta
       (capacity & (capacity - 1)) != 0)
     return pcs_set_einval("pcs_voxel_hash_find", "bad arguments");
   if (nq == 0) return 0;
-  hipLaunchKernelGGL(hash_find_kernel, dim3(blocks_for_n(nq)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(hash_find_kernel, dim3(blocks_1d(nq)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                      table_keys, table_vals, (uint64_t)(capacity - 1), queries, nq, out);
   PCS_CHECK_LAUNCH();
   return 0;
@@ -208,7 +191,7 @@ extern "C" int pcs_sparse_neighbors(const uint64_t *table_keys, const int32_t *t
       capacity < 1 || (capacity & (capacity - 1)) != 0)
     return pcs_set_einval("pcs_sparse_neighbors", "bad arguments");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(neighbors_kernel, dim3(blocks_for_n(n * 27)), dim3(THREADS), 0,
+  hipLaunchKernelGGL(neighbors_kernel, dim3(blocks_1d(n * 27)), dim3(THREADS), 0,
                      reinterpret_cast<hipStream_t>(stream), table_keys, table_vals, (uint64_t)(capacity - 1), keys, n,
                      (int)grid, nbr);
   PCS_CHECK_LAUNCH();
@@ -223,7 +206,7 @@ extern "C" int pcs_sparse_coarse_keys(const uint64_t *keys, int64_t n, int32_t g
   if (n < 0 || n > ((int64_t)1 << 31) || (n > 0 && (!keys || !parent_key || !tap)))
     return pcs_set_einval("pcs_sparse_coarse_keys", "keys, parent_key and tap are required (0 <= n <= 2^31)");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(coarse_keys_kernel, dim3(blocks_for_n(n)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(coarse_keys_kernel, dim3(blocks_1d(n)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                      keys, n, (int)grid, parent_key, tap);
   PCS_CHECK_LAUNCH();
   return 0;
@@ -237,9 +220,9 @@ extern "C" int pcs_sparse_coarse_maps(const int64_t *coarse_row, const int32_t *
                           "coarse_row, tap, child, parent and up are required (n_coarse <= n_fine < 2^28)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (n_coarse > 0)
-    hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks_for_n(n_coarse * 8)), dim3(THREADS), 0, s, child, n_coarse * 8, -1);
+    hipLaunchKernelGGL(fill_i32_kernel, dim3(blocks_1d(n_coarse * 8)), dim3(THREADS), 0, s, child, n_coarse * 8, -1);
   if (n_fine > 0)
-    hipLaunchKernelGGL(coarse_maps_kernel, dim3(blocks_for_n(n_fine)), dim3(THREADS), 0, s, coarse_row, tap, n_fine,
+    hipLaunchKernelGGL(coarse_maps_kernel, dim3(blocks_1d(n_fine)), dim3(THREADS), 0, s, coarse_row, tap, n_fine,
                        n_coarse, child, parent, up);
   PCS_CHECK_LAUNCH();
   return 0;

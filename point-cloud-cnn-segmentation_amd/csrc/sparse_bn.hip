@@ -10,72 +10,17 @@
 //               S2 = sum dz (x - mean) rstd, summed over the blocks by pcs_bn_bwd_finalize
 //   bwd_apply   dx = fma(alpha[c], dz, fma(gamma_c[c], x, beta_c[c]))
 //
-// All four are bandwidth-bound streams (no MFMA): a row of C channels is C / E lanes of E elements
-// (E = 8 when either side is bf16, else 4: 16 bytes of the narrower type), a workgroup holds
-// 256 / (C / E) rows per pass (the lanes left over when C / E does not divide 256 idle), and every
-// lane issues the loads of UNROLL passes before it uses the first.  Arithmetic is fp32.  Nothing is
-// added atomically, every output row is stored once and every sum runs in a fixed order: results
-// are bitwise reproducible.
-#include "common.h"
+// All four are bandwidth-bound streams (no MFMA) over the lanes-of-E-elements row scheme of
+// row_piece.h, and every lane issues the loads of UNROLL passes before it uses the first.
+// Arithmetic is fp32.  Nothing is added atomically, every output row is stored once and every sum
+// runs in a fixed order: results are bitwise reproducible.
+#include "row_piece.h"
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int UNROLL = 4;          // row passes a lane keeps in flight
-constexpr int MAX_C = 1024;
-constexpr int ROW_TILE = 64;       // rows per block are a multiple of this
-constexpr int MAX_BLOCKS = 2048;   // of the two reductions (~8 per CU)
+using namespace pcs_rows;
 
-template <typename A, typename B>
-struct Piece {
-  static constexpr int E = (Elem<A>::EPC == 8 || Elem<B>::EPC == 8) ? 8 : 4;
-};
-
-// a lane's E elements of a row as raw 16-byte registers: loads first, conversion at the use
-template <typename T, int E>
-struct Raw {
-  static constexpr int NQ = E * Elem<T>::SIZE / 16;
-  u32x4 q[NQ];
-};
-
-template <typename T, int E>
-PCS_DEV void raw_load(Raw<T, E> &r, const T *__restrict__ p, bool present) {
-#pragma unroll
-  for (int i = 0; i < Raw<T, E>::NQ; ++i)
-    r.q[i] = present ? reinterpret_cast<const u32x4 *>(p)[i] : mk_u32x4(0u, 0u, 0u, 0u);
-}
-
-template <typename T, int E>
-PCS_DEV void raw_unpack(const Raw<T, E> &r, float (&v)[E]) {
-  constexpr int EPC = Elem<T>::EPC;
-#pragma unroll
-  for (int i = 0; i < Raw<T, E>::NQ; ++i) {
-    float t[EPC];
-    unpack_chunk(r.q[i], t);
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) v[i * EPC + e] = t[e];
-  }
-}
-
-template <typename T, int E>
-PCS_DEV void store_piece(T *__restrict__ p, const float (&v)[E]) {
-  constexpr int EPC = Elem<T>::EPC;
-#pragma unroll
-  for (int i = 0; i < E / EPC; ++i) {
-    float t[EPC];
-#pragma unroll
-    for (int e = 0; e < EPC; ++e) t[e] = v[i * EPC + e];
-    st16(reinterpret_cast<u32x4 *>(p) + i, pack_chunk(t));
-  }
-}
-
-// this thread's (row slot r0, piece cc) in a workgroup of rpp = 256 / lpr rows; false: a lane left over
-PCS_DEV bool lane_slot(int lpr, int &rpp, int &r0, int &cc) {
-  rpp = THREADS / lpr;
-  r0 = (int)threadIdx.x / lpr;
-  cc = (int)threadIdx.x - r0 * lpr;
-  return r0 < rpp;
-}
+constexpr int UNROLL = 4;   // row passes a lane keeps in flight
 
 // rows lo + j, lo + j + rpp, ... below lo + n: how many slot j reads (per = n / rpp, rem = n % rpp)
 PCS_DEV float slot_rows(int64_t per, int rem, int j) { return (float)(per + (j < rem ? 1 : 0)); }
@@ -167,7 +112,7 @@ __global__ __launch_bounds__(THREADS) void sbn_apply_kernel(const XT *__restrict
           if (R) pre += a[e];
           x[e] = act ? relu(pre) : pre;
         }
-        store_piece<YT, E>(Y + row * C + c0, x);
+        store_piece<YT, E, true>(Y + row * C + c0, x);
       }
     }
   }
@@ -219,7 +164,7 @@ __global__ __launch_bounds__(THREADS) void sbn_bwd_reduce_kernel(const YT *__res
             s1[e] += dz[e];
             s2[e] = fmaf(dz[e], (x[e] - mu[e]) * rs[e], s2[e]);
           }
-          if (DZ) store_piece<YT, E>(DZ + row * C + c0, dz);
+          if (DZ) store_piece<YT, E, true>(DZ + row * C + c0, dz);
         }
       }
     }
@@ -268,21 +213,10 @@ __global__ __launch_bounds__(THREADS) void sbn_bwd_apply_kernel(const YT *__rest
         raw_unpack<XT, E>(rx[u], x);
 #pragma unroll
         for (int e = 0; e < E; ++e) x[e] = fmaf(ca[e], dz[e], fmaf(cg[e], x[e], cb[e]));
-        store_piece<XT, E>(dX + row * C + c0, x);
+        store_piece<XT, E, true>(dX + row * C + c0, x);
       }
     }
   }
-}
-
-bool known(int32_t dtype) { return dtype == PCS_F32 || dtype == PCS_BF16; }
-
-// C a multiple of the piece (8 when either side is bf16, else 4) and at most 1024
-const char *check_shape(int32_t xdtype, int32_t ydtype, int32_t C) {
-  if (!known(xdtype) || !known(ydtype)) return "unknown dtype (PCS_F32 | PCS_BF16)";
-  const int e = (xdtype == PCS_BF16 || ydtype == PCS_BF16) ? 8 : 4;
-  if (C < e || C % e != 0 || C > MAX_C)
-    return "C % 8 == 0 (bf16 on either side) or C % 4 == 0 (fp32), C <= 1024 required";
-  return nullptr;
 }
 
 // the blocks tile [0, V) and none is empty
@@ -300,15 +234,6 @@ int stream_blocks(int64_t V, int32_t C, int e) {
   return (int)(b > (1 << 16) ? (1 << 16) : b);
 }
 
-// the dtype pair as template arguments
-#define PCS_SBN_PAIRS(xdtype, ydtype, CALL)                                   \
-  do {                                                                       \
-    if (xdtype == PCS_BF16 && ydtype == PCS_BF16) { CALL(bf16_t, bf16_t); } \
-    else if (xdtype == PCS_BF16) { CALL(bf16_t, float); }                   \
-    else if (ydtype == PCS_BF16) { CALL(float, bf16_t); }                   \
-    else { CALL(float, float); }                                             \
-  } while (0)
-
 }  // namespace
 
 extern "C" int64_t pcs_sparse_bn_geometry(int64_t V, int32_t C, int32_t *num_blocks) {
@@ -316,16 +241,15 @@ extern "C" int64_t pcs_sparse_bn_geometry(int64_t V, int32_t C, int32_t *num_blo
   if (V < 0) return pcs_set_einval("pcs_sparse_bn_geometry", "V >= 0 required");
   if (C < 4 || C % 4 != 0 || C > MAX_C)
     return pcs_set_einval("pcs_sparse_bn_geometry", "C % 4 == 0, 4 <= C <= 1024 required");
-  const int64_t span = (int64_t)ROW_TILE * MAX_BLOCKS;
-  const int64_t rpb = ROW_TILE * pcs_max64((V + span - 1) / span, 1);
-  *num_blocks = (int32_t)((V + rpb - 1) / rpb);   // 0 for an empty level
-  return rpb;
+  const Blocks b = reduction_blocks(V, ROW_TILE);
+  *num_blocks = b.n;   // 0 for an empty level
+  return b.per;
 }
 
 extern "C" int pcs_sparse_bn_stats(const void *X, int32_t xdtype, int64_t V, int32_t C, int32_t num_blocks,
                                    int64_t rows_per_block, float *stats, pcs_stream_t stream) {
   if (V < 0) return pcs_set_einval("pcs_sparse_bn_stats", "V >= 0 required");
-  if (const char *msg = check_shape(xdtype, xdtype, C)) return pcs_set_einval("pcs_sparse_bn_stats", msg);
+  if (const char *msg = check_width(xdtype, xdtype, C, true)) return pcs_set_einval("pcs_sparse_bn_stats", msg);
   if (V == 0) return 0;
   if (!X || !stats) return pcs_set_einval("pcs_sparse_bn_stats", "NULL pointer");
   if (const char *msg = check_blocks(V, num_blocks, rows_per_block)) return pcs_set_einval("pcs_sparse_bn_stats", msg);
@@ -344,16 +268,17 @@ extern "C" int pcs_sparse_bn_apply(const void *X, int32_t xdtype, const void *R,
                                    const float *shift, int32_t relu, int64_t V, int32_t C, void *Y, int32_t ydtype,
                                    pcs_stream_t stream) {
   if (V < 0) return pcs_set_einval("pcs_sparse_bn_apply", "V >= 0 required");
-  if (const char *msg = check_shape(xdtype, ydtype, C)) return pcs_set_einval("pcs_sparse_bn_apply", msg);
+  if (const char *msg = check_width(xdtype, ydtype, C, true)) return pcs_set_einval("pcs_sparse_bn_apply", msg);
   if (V == 0) return 0;
   if (!X || !scale || !shift || !Y) return pcs_set_einval("pcs_sparse_bn_apply", "NULL pointer");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define PCS_SBN_CALL(XT, YT)                                                                                        \
-  hipLaunchKernelGGL((sbn_apply_kernel<XT, YT>), dim3(stream_blocks(V, C, Piece<XT, YT>::E)), dim3(THREADS), 0, s, \
-                     static_cast<const XT *>(X), static_cast<const YT *>(R), scale, shift, (int)(relu != 0), V,     \
-                     (int)C, static_cast<YT *>(Y))
-  PCS_SBN_PAIRS(xdtype, ydtype, PCS_SBN_CALL);
-#undef PCS_SBN_CALL
+  for_dtype_pair(xdtype, ydtype, [&](auto x, auto y) {
+    using XT = decltype(x);
+    using YT = decltype(y);
+    hipLaunchKernelGGL((sbn_apply_kernel<XT, YT>), dim3(stream_blocks(V, C, Piece<XT, YT>::E)), dim3(THREADS), 0, s,
+                       static_cast<const XT *>(X), static_cast<const YT *>(R), scale, shift, (int)(relu != 0), V,
+                       (int)C, static_cast<YT *>(Y));
+  });
   PCS_CHECK_LAUNCH();
   return 0;
 }
@@ -363,7 +288,7 @@ extern "C" int pcs_sparse_bn_bwd_reduce(const void *dY, const void *Y, int32_t y
                                         int32_t num_blocks, int64_t rows_per_block, void *DZ, float *stats,
                                         pcs_stream_t stream) {
   if (V < 0) return pcs_set_einval("pcs_sparse_bn_bwd_reduce", "V >= 0 required");
-  if (const char *msg = check_shape(xdtype, ydtype, C)) return pcs_set_einval("pcs_sparse_bn_bwd_reduce", msg);
+  if (const char *msg = check_width(xdtype, ydtype, C, true)) return pcs_set_einval("pcs_sparse_bn_bwd_reduce", msg);
   if (V == 0) return 0;
   if (!dY || !X || !mean || !rstd || !stats) return pcs_set_einval("pcs_sparse_bn_bwd_reduce", "NULL pointer");
   if (relu && (!Y || !DZ))
@@ -371,12 +296,13 @@ extern "C" int pcs_sparse_bn_bwd_reduce(const void *dY, const void *Y, int32_t y
   if (const char *msg = check_blocks(V, num_blocks, rows_per_block))
     return pcs_set_einval("pcs_sparse_bn_bwd_reduce", msg);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define PCS_SBN_CALL(XT, YT)                                                                                       \
-  hipLaunchKernelGGL((sbn_bwd_reduce_kernel<XT, YT>), dim3(num_blocks), dim3(THREADS), 0, s,                      \
-                     static_cast<const YT *>(dY), static_cast<const YT *>(Y), static_cast<const XT *>(X), mean,    \
-                     rstd, (int)(relu != 0), V, (int)C, rows_per_block, static_cast<YT *>(DZ), stats)
-  PCS_SBN_PAIRS(xdtype, ydtype, PCS_SBN_CALL);
-#undef PCS_SBN_CALL
+  for_dtype_pair(xdtype, ydtype, [&](auto x, auto y) {
+    using XT = decltype(x);
+    using YT = decltype(y);
+    hipLaunchKernelGGL((sbn_bwd_reduce_kernel<XT, YT>), dim3(num_blocks), dim3(THREADS), 0, s,
+                       static_cast<const YT *>(dY), static_cast<const YT *>(Y), static_cast<const XT *>(X), mean,
+                       rstd, (int)(relu != 0), V, (int)C, rows_per_block, static_cast<YT *>(DZ), stats);
+  });
   PCS_CHECK_LAUNCH();
   return 0;
 }
@@ -385,17 +311,18 @@ extern "C" int pcs_sparse_bn_bwd_apply(const void *DZ, int32_t ydtype, const voi
                                        const float *alpha, const float *beta_c, const float *gamma_c, int64_t V,
                                        int32_t C, void *dX, pcs_stream_t stream) {
   if (V < 0) return pcs_set_einval("pcs_sparse_bn_bwd_apply", "V >= 0 required");
-  if (const char *msg = check_shape(xdtype, ydtype, C)) return pcs_set_einval("pcs_sparse_bn_bwd_apply", msg);
+  if (const char *msg = check_width(xdtype, ydtype, C, true)) return pcs_set_einval("pcs_sparse_bn_bwd_apply", msg);
   if (V == 0) return 0;
   if (!DZ || !X || !alpha || !beta_c || !gamma_c || !dX)
     return pcs_set_einval("pcs_sparse_bn_bwd_apply", "NULL pointer");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define PCS_SBN_CALL(XT, YT)                                                                                       \
-  hipLaunchKernelGGL((sbn_bwd_apply_kernel<XT, YT>), dim3(stream_blocks(V, C, Piece<XT, YT>::E)), dim3(THREADS), 0, \
-                     s, static_cast<const YT *>(DZ), static_cast<const XT *>(X), alpha, beta_c, gamma_c, V, (int)C, \
-                     static_cast<XT *>(dX))
-  PCS_SBN_PAIRS(xdtype, ydtype, PCS_SBN_CALL);
-#undef PCS_SBN_CALL
+  for_dtype_pair(xdtype, ydtype, [&](auto x, auto y) {
+    using XT = decltype(x);
+    using YT = decltype(y);
+    hipLaunchKernelGGL((sbn_bwd_apply_kernel<XT, YT>), dim3(stream_blocks(V, C, Piece<XT, YT>::E)), dim3(THREADS), 0,
+                       s, static_cast<const YT *>(DZ), static_cast<const XT *>(X), alpha, beta_c, gamma_c, V, (int)C,
+                       static_cast<XT *>(dX));
+  });
   PCS_CHECK_LAUNCH();
   return 0;
 }

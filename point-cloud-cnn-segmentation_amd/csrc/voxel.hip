@@ -4,7 +4,8 @@
 // restatement in oracle/voxel_oracle.py, labelled "not reference parity".
 //
 //   voxel id   v(p) = (ix * G + iy) * G + iz,  ix = clamp(floor((x - lo_x) / (hi_x - lo_x) * G), 0, G-1)
-//              (fp32, IEEE division and multiply in this order: bit-exact with numpy float32)
+//              (fp32, IEEE division and multiply in this order: bit-exact with numpy float32;
+//              voxel_of, voxel_geom.h)
 //   key        scene(p) * G^3 + v(p)  (uint64), sorted stably with the point index as value
 //   voxels     one per distinct key, in key order (scene-major, then voxel id):
 //              x, y, z = mean of its points, e = sum of its points' e (fp32 sums in the sorted,
@@ -16,29 +17,18 @@
 // Integer work is bit-exact by construction (radix sort, flag + scan, per-segment loops);
 // the per-voxel float sums run sequentially in a fixed order, so results are deterministic.
 #include "common.h"
+#include "voxel_geom.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 namespace {
 
+using pcs_geom::blocks_1d;
+using pcs_geom::Box;
+using pcs_geom::voxel_of;
+
 constexpr int THREADS = 256;
-
-struct Box {
-  float lo[3], hi[3];
-};
-
-PCS_DEV int64_t voxel_of(const float *p, int G, const Box &b) {
-  int64_t id = 0;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const float t = (p[d] - b.lo[d]) / (b.hi[d] - b.lo[d]);
-    int i = (int)floorf(t * (float)G);
-    i = i < 0 ? 0 : (i > G - 1 ? G - 1 : i);
-    id = id * G + i;
-  }
-  return id;
-}
 
 __global__ __launch_bounds__(THREADS) void voxel_ids_kernel(const float *__restrict__ pts, int64_t T, int G, Box b,
                                                             int64_t *__restrict__ ids) {
@@ -156,8 +146,6 @@ __global__ __launch_bounds__(THREADS) void padded_index_kernel(const int64_t *__
   }
 }
 
-int blocks(int64_t n) { return (int)pcs_max64(1, pcs_min64(8192, (n + THREADS - 1) / THREADS)); }
-
 struct VoxWs {   // workspace carve-up (all 256-B aligned)
   uint64_t *keys, *skeys;
   int64_t *vals, *perm, *flags, *seg, *start;
@@ -200,7 +188,7 @@ extern "C" int pcs_voxel_ids(const float *points, int64_t T, int32_t grid, float
     return pcs_set_einval("pcs_voxel_ids", "bad arguments (grid in [1, 2^20], hi > lo)");
   if (T == 0) return 0;
   const Box b = {{lo_x, lo_y, lo_z}, {hi_x, hi_y, hi_z}};
-  hipLaunchKernelGGL(voxel_ids_kernel, dim3(blocks(T)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(voxel_ids_kernel, dim3(blocks_1d(T)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                      points, T, (int)grid, b, ids);
   PCS_CHECK_LAUNCH();
   return 0;
@@ -230,7 +218,7 @@ extern "C" int pcs_voxelize(const float *points, const int64_t *labels, const in
   if (carve(workspace, (size_t)workspace_bytes, T, w, nullptr)) return pcs_set_einval("pcs_voxelize", "workspace too small");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const Box b = {{lo_x, lo_y, lo_z}, {hi_x, hi_y, hi_z}};
-  hipLaunchKernelGGL(voxel_keys_kernel, dim3(blocks(T)), dim3(THREADS), 0, s, points, offsets, (int)num_scenes, T,
+  hipLaunchKernelGGL(voxel_keys_kernel, dim3(blocks_1d(T)), dim3(THREADS), 0, s, points, offsets, (int)num_scenes, T,
                      (int)grid, b, w.keys, w.vals);
   PCS_CHECK_LAUNCH();
   int bits = 1;
@@ -238,14 +226,14 @@ extern "C" int pcs_voxelize(const float *points, const int64_t *labels, const in
   size_t tb = w.tmp_bytes;
   if (rocprim::radix_sort_pairs(w.tmp, tb, w.keys, w.skeys, w.vals, w.perm, (size_t)T, 0, bits, s) != hipSuccess)
     return pcs_set_einval("pcs_voxelize", "radix sort failed");
-  hipLaunchKernelGGL(head_flags_kernel, dim3(blocks(T)), dim3(THREADS), 0, s, w.skeys, T, w.flags);
+  hipLaunchKernelGGL(head_flags_kernel, dim3(blocks_1d(T)), dim3(THREADS), 0, s, w.skeys, T, w.flags);
   PCS_CHECK_LAUNCH();
   tb = w.tmp_bytes;
   if (rocprim::inclusive_scan(w.tmp, tb, w.flags, w.seg, (size_t)T, rocprim::plus<int64_t>(), s) != hipSuccess)
     return pcs_set_einval("pcs_voxelize", "scan failed");
-  hipLaunchKernelGGL(seg_starts_kernel, dim3(blocks(T)), dim3(THREADS), 0, s, w.seg, T, w.start, num_voxels);
+  hipLaunchKernelGGL(seg_starts_kernel, dim3(blocks_1d(T)), dim3(THREADS), 0, s, w.seg, T, w.start, num_voxels);
   PCS_CHECK_LAUNCH();
-  hipLaunchKernelGGL(aggregate_kernel, dim3(blocks(T)), dim3(THREADS), 0, s, points, labels, w.skeys, w.perm, w.start,
+  hipLaunchKernelGGL(aggregate_kernel, dim3(blocks_1d(T)), dim3(THREADS), 0, s, points, labels, w.skeys, w.perm, w.start,
                      num_voxels, (int)num_classes, reinterpret_cast<f32x4 *>(vox_points), vox_labels, vox_counts,
                      voxel_of_point);
   PCS_CHECK_LAUNCH();
@@ -259,7 +247,7 @@ extern "C" int pcs_gather_rows(const float *src, int64_t ld_src, const int64_t *
                                float *dst, pcs_stream_t stream) {
   if (!src || !idx || !dst || n < 0 || C < 1 || ld_src < C) return pcs_set_einval("pcs_gather_rows", "bad arguments");
   if (n == 0) return 0;
-  hipLaunchKernelGGL(gather_rows_kernel, dim3(blocks(n * C)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(blocks_1d(n * C)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                      src, ld_src, idx, n, (int)C, dst);
   PCS_CHECK_LAUNCH();
   return 0;
@@ -270,7 +258,7 @@ extern "C" int pcs_voxel_padded_index(const int64_t *voxel_of_point, int64_t T, 
   if (!voxel_of_point || !vox_offsets || !out || T < 0 || num_scenes < 1 || scene_rows < 0)
     return pcs_set_einval("pcs_voxel_padded_index", "bad arguments");
   if (T == 0) return 0;
-  hipLaunchKernelGGL(padded_index_kernel, dim3(blocks(T)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(padded_index_kernel, dim3(blocks_1d(T)), dim3(THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                      voxel_of_point, T, vox_offsets, (int)num_scenes, scene_rows, out);
   PCS_CHECK_LAUNCH();
   return 0;
