@@ -1,0 +1,200 @@
+"""Does the host side issue the same library calls as another copy of the package?  (needs a GPU)
+
+    python tools/engine_trace.py [SCENARIO ...]                    print the traces of the in-tree package
+    python tools/engine_trace.py --against PKGDIR [SCENARIO ...]   compare PKGDIR with the in-tree package
+    python tools/engine_trace.py --against PKGDIR --tree PKGDIR2   ... with the package at PKGDIR2 instead
+
+The counterpart of tools/asm_equal.py for a refactor of the orchestration (engine.py) that must
+not change what runs.  PKGDIR is a copy of point-cloud-cnn-segmentation_amd/ as it was at the
+revision to compare with (`git archive REV point-cloud-cnn-segmentation_amd | tar -x -C DIR`); its
+csrc/ is not used: both sides load the in-tree libpcs.so (PCS_LIB).  Each side runs every scenario
+in a fresh child process.  A scenario's trace is one line per call on the loaded library, through
+_lib.call, _lib.workspace or directly: the function, every scalar argument and scalar struct field,
+NULL / ptr for every pointer, main / side for the stream, a size query's return value, and
+torch.cuda.memory_allocated() at the call; the tags and counts of Engine.timing follow where a
+scenario records them.  Its outputs (loss, flat gradients, parameters, Adam state, BatchNorm
+buffers, logits) are compared bit for bit by their SHA-256.  Prints per scenario `identical` or the
+first differing lines and the outputs that differ.  Exit status 1 if any scenario differs, 2 if a
+child process failed.
+
+Scenarios (all on synthetic_batch(11, [4113, 3000], 2, grid=32), the batch of
+tests/test_gpu_buckets.py): step:DTYPE[:TWEAK] two fused training steps with one dropout seed;
+dropin:DTYPE model(x), a loss on the logits, .backward(); eval:DTYPE[:TRUNK]; timing:bf16."""
+import ctypes as ct
+import hashlib
+import importlib.util
+import json
+import os
+import subprocess
+import sys
+import tempfile
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TREE = os.path.join(REPO, "point-cloud-cnn-segmentation_amd")
+TWEAKS = {"generic": ("flags", 1), "no_glds": ("flags", 2), "unfused12": ("fused_seg12", False),
+          "draw_first": ("draw_beside_gram", False), "independent": ("dropout_draw", "independent"), "masks": None}
+SCENARIOS = ([f"step:{d}" for d in ("fp32", "bf16", "fp8")] + [f"step:bf16:{t}" for t in TWEAKS]
+             + ["dropin:fp32", "dropin:bf16", "eval:fp32", "eval:bf16:fp32", "eval:bf16:bf16", "eval:fp8", "timing:bf16"])
+
+
+class Trace:
+    """Stands in for the loaded CDLL: forwards every call and keeps one line for it."""
+
+    def __init__(self, lib, signatures, mem):
+        self.lib, self.mem, self.lines, self.main = lib, mem, [], None
+        self.sigs = {name: (res, args) for name, res, args in signatures if args}
+
+    def __getattr__(self, name):
+        fn = getattr(self.lib, name)
+        if name not in self.sigs:
+            return fn
+        res, argtypes = self.sigs[name]
+
+        def call(*args):
+            shown = [self.show(a, t, launch=res is ct.c_int and i == len(args) - 1)
+                     for i, (a, t) in enumerate(zip(args, argtypes))]
+            head = f"{name}({', '.join(shown)}) mem={self.mem()}"
+            r = fn(*args)
+            self.lines.append(head if res is ct.c_int else f"{head} -> {r}")
+            return r
+        return call
+
+    def show(self, a, t, launch=False):
+        if t is ct.c_void_p:
+            if launch:   # the last argument of every launch is its stream
+                return "main" if (a or 0) == self.main else "side"
+            return "ptr" if a else "NULL"
+        if isinstance(t, type) and issubclass(t, ct._Pointer):
+            obj = a._obj
+            if isinstance(obj, ct.Structure):
+                return "{" + " ".join(f"{f}={self.show(getattr(obj, f), ft)}" for f, ft in obj._fields_) + "}"
+            return f"*{obj.value}"
+        return repr(float(a)) if t is ct.c_float else str(int(a))
+
+
+def load_package(pkgdir):
+    """Import the package directory ``pkgdir`` as pcs_amd (what the repository's pcs_amd.py does)."""
+    spec = importlib.util.spec_from_file_location("pcs_amd", os.path.join(pkgdir, "__init__.py"),
+                                                  submodule_search_locations=[pkgdir])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules["pcs_amd"] = mod
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def digest(t):
+    t = t.detach().contiguous().cpu()
+    return hashlib.sha256(t.view(-1).view(torch.uint8).numpy().tobytes()).hexdigest()[:16]
+
+
+def run_scenario(name, trace):
+    """Run one scenario with ``trace`` recording; returns {output name: digest}."""
+    from pcs_amd.data import synthetic_batch
+    from pcs_amd.model import PointNetSegmentation
+    from pcs_amd.train import FusedTrainStep
+    kind, dtype, *opt = name.split(":")
+    dev = torch.device("cuda")
+    torch.manual_seed(5)
+    trunk = opt[0] if kind == "eval" and opt else "fp32"
+    model = PointNetSegmentation(2, compute_dtype=dtype, eval_trunk=trunk).to(dev)
+    pts, lab, _ = synthetic_batch(11, [4096 + 17, 3000], 2, grid=32)
+    x, y = torch.from_numpy(pts).to(dev), torch.from_numpy(lab).to(dev)
+    out, masks = {}, None
+    if kind == "step" and opt and TWEAKS[opt[0]]:
+        attr, value = TWEAKS[opt[0]]
+        setattr(model if attr == "dropout_draw" else model._engine(), attr, value)
+    torch.cuda.synchronize()
+    trace.lines, trace.main = [], torch.cuda.current_stream().cuda_stream
+    if kind == "eval":
+        model.eval()
+        with torch.no_grad():
+            out["logits"] = model(x)
+    elif kind == "dropin":
+        model.train()
+        out["logits"] = model(x)
+        out["loss"] = torch.nn.functional.cross_entropy(out["logits"].reshape(-1, 2), y.reshape(-1), ignore_index=-1)
+        out["loss"].backward()
+        out.update({f"grad.{n}": p.grad for n, p in model.named_parameters()})
+    else:
+        step = FusedTrainStep(model, class_weight=[0.7, 1.3])
+        step.timing = {} if kind == "timing" else None
+        for i in range(1 if kind == "timing" else 2):
+            if opt == ["masks"]:
+                g = torch.Generator().manual_seed(3)
+                model.set_dropout_masks(*(torch.randint(0, 256, (x.shape[0] * x.shape[1], w), dtype=torch.uint8,
+                                                        generator=g).to(dev) for w in (64, 32)))
+                masks = model._take_dropout_masks()
+            out[f"loss{i}"] = step(x, y, masks=masks, seed=77)
+        pflat, gflat = sys.modules["pcs_amd.optim"].flat_buffers(model)
+        out.update(gflat=gflat, pflat=pflat, exp_avg=step.opt.exp_avg, exp_avg_sq=step.opt.exp_avg_sq)
+        torch.cuda.synchronize()
+        trace.lines += [f"timing {tag} x{len(ev)}" for tag, ev in sorted((step.timing or {}).items())]
+    out.update({f"buf.{n}": b for n, b in model.named_buffers()})
+    torch.cuda.synchronize()
+    return {k: digest(v) for k, v in out.items()}
+
+
+def child(pkgdir, names, result):
+    global torch
+    import torch
+    load_package(pkgdir)
+    L = importlib.import_module("pcs_amd._lib")
+    trace = L._lib = Trace(L.load(), L.SIGNATURES, torch.cuda.memory_allocated)
+    res = {}
+    for name in names:
+        outs = run_scenario(name, trace)
+        res[name] = {"trace": trace.lines, "out": outs}
+    with open(result, "w") as f:
+        json.dump(res, f)
+
+
+def run_side(pkgdir, names, tmp):
+    result = os.path.join(tmp, f"side{len(os.listdir(tmp))}.json")
+    env = dict(os.environ, PCS_LIB=os.path.join(TREE, "csrc", "libpcs.so"))
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", os.path.abspath(pkgdir), result, *names],
+                       env=env)
+    if r.returncode:   # (not a difference: the caller must not go on using the GPU after a fault)
+        print(f"the run of {pkgdir} ended with status {r.returncode}")
+        sys.exit(2)
+    return json.load(open(result))
+
+
+def main(argv):
+    opts = {}
+    for flag in ("--against", "--tree"):
+        if flag in argv:
+            i = argv.index(flag)
+            opts[flag] = argv[i + 1]
+            del argv[i:i + 2]
+    names = argv or SCENARIOS
+    with tempfile.TemporaryDirectory() as tmp:
+        new = run_side(opts.get("--tree", TREE), names, tmp)
+        if "--against" not in opts:
+            for n in names:
+                print(f"== {n}\n" + "\n".join(new[n]["trace"]) + f"\n{json.dumps(new[n]['out'], indent=1)}")
+            return 0
+        old = run_side(opts["--against"], names, tmp)
+    bad = 0
+    for n in names:
+        a, b = old[n], new[n]
+        outs = [k for k in sorted(set(a["out"]) | set(b["out"])) if a["out"].get(k) != b["out"].get(k)]
+        if a["trace"] == b["trace"] and not outs:
+            print(f"{n:24s} identical   ({len(a['trace'])} calls, {len(a['out'])} outputs)")
+            continue
+        bad += 1
+        print(f"{n:24s} DIFFERS" + (f"   outputs: {' '.join(outs)}" if outs else ""))
+        if a["trace"] != b["trace"]:
+            first = next((i for i, (p, q) in enumerate(zip(a["trace"], b["trace"])) if p != q),
+                         min(len(a["trace"]), len(b["trace"])))
+            for side, t in ((opts["--against"], a["trace"]), (opts.get("--tree", "tree"), b["trace"])):
+                print(f"    {side}: {len(t)} calls, from call {first}:")
+                print("".join(f"        {ln}\n" for ln in t[first:first + 3]), end="")
+    print(f"{len(names) - bad} of {len(names)} scenarios identical")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    if sys.argv[1:2] == ["--child"]:
+        child(sys.argv[2], sys.argv[4:], sys.argv[3])
+    else:
+        sys.exit(main(sys.argv[1:]))
