@@ -1,5 +1,9 @@
 """ctypes binding of the C ABI in include/pcs.h (libpcs.so, built in-tree for gfx950).
 
+The header is the table: its structs, prototypes, enumerators and PCS_ABI_VERSION are parsed once
+at import into the ``ct.Structure`` classes, ``SIGNATURES`` and the constants below, so a new entry
+point is declared in the header only (tests/golden/abi_tables.json records the result).
+
 There is no fallback: if the library is missing or fails to load, every GPU entry point
 raises.  ``torch`` is imported first so that the HIP runtime torch ships (same SONAME
 ``libamdhip64.so.7``) is the one the library binds to -- one runtime per process.
@@ -8,230 +12,156 @@ from __future__ import annotations
 
 import ctypes as ct
 import os
+import re
 
 import torch  # noqa: F401  (loads torch's HIP runtime before libpcs.so)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libpcs.so")
+HEADER_PATH = os.path.join(_HERE, "..", "include", "pcs.h")   # csrc/Makefile's ../../include/pcs.h
 
-F32, BF16, FP8 = 0, 1, 2
-PRO_RAW, PRO_BNRELU, PRO_BWD, PRO_CAT = 0, 1, 2, 4
-EPI_FWD, EPI_DGRAD, EPI_RAW, EPI_BNRELU = 0, 1, 2, 3
-HEAD_FWD, HEAD_CE, HEAD_BWD = 0, 1, 2
-
-_vp = ct.c_void_p
-_i64 = ct.c_int64
-_i32 = ct.c_int32
-_f = ct.c_float
-
-
-class GemmArgs(ct.Structure):
-    _fields_ = [
-        ("num_scenes", _i64), ("scene_rows", _i64),
-        ("K", _i32), ("Ncols", _i32), ("dtype", _i32), ("prologue", _i32), ("epilogue", _i32),
-        ("chunks_per_scene", _i32),
-        ("A", _vp), ("A2", _vp), ("pa", _vp), ("pb", _vp), ("pc", _vp), ("a_mask", _vp),
-        ("a_keep_scale", _f),
-        ("pool_idx", _vp), ("pool_coef", _vp),
-        ("W", _vp), ("C", _vp), ("bias", _vp), ("scene_bias", _vp), ("addend", _vp),
-        ("c_mask", _vp), ("c_keep_scale", _f),
-        ("Yp", _vp), ("es", _vp), ("et", _vp), ("emean", _vp), ("erstd", _vp),
-        ("stats", _vp), ("pool", _vp), ("flags", _i32),
-        ("pool_w", _vp), ("pool_ldw", _i64), ("pool_c", _i32), ("w_scale", _vp),
-        ("W2", _vp), ("K1", _i32), ("gram", _vp),
-    ]
+_SCALARS = {"int": ct.c_int, "int32_t": ct.c_int32, "int64_t": ct.c_int64, "uint64_t": ct.c_uint64,
+            "float": ct.c_float}
+_POINTEES = {*_SCALARS, "void", "uint8_t", "char"}
+_DECL = re.compile(r"(const\s+)?(\w+)\s*(\*?)\s*(\w+)$")      # [const] TYPE [*]NAME
+_ITEMS = [(kind, re.compile(r"\s*" + rx)) for kind, rx in (
+    ("opaque", r"typedef\s+struct\s+\w+\s*\*\s*(\w+)\s*;"),
+    ("struct", r"typedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;"),
+    ("enum", r"enum\s*\{([^{}]*)\}\s*;"),
+    ("function", r"((?:const\s+)?\w+\s*\*?)\s*(\w+)\s*\(([^(){};]*)\)\s*;"))]
 
 
-FLAG_GENERIC = 1
-FLAG_NO_GLDS = 2
-FLAG_AW_FP8 = 4
-FLAG_C_FP8 = 8
-FLAG_POOL_SIGNED_W = 16
+def _fail(what, text):
+    raise ImportError(f"include/pcs.h: {what}: {' '.join(text.split())[:100]!r}")
 
 
-class WgradArgs(ct.Structure):
-    _fields_ = [
-        ("num_scenes", _i64), ("scene_rows", _i64),
-        ("Cout", _i32), ("Cin", _i32), ("dtype", _i32), ("splits_per_scene", _i32),
-        ("dy_mode", _i32),
-        ("dZ", _vp), ("Y", _vp), ("alpha", _vp), ("beta", _vp), ("gamma", _vp),
-        ("reserved0", _vp), ("reserved1", _vp),
-        ("x_mode", _i32),
-        ("X", _vp), ("s", _vp), ("t", _vp), ("x_mask", _vp), ("x_keep_scale", _f),
-        ("partial", _vp), ("dW", _vp), ("ldw", _i64), ("flags", _i32), ("reserved2", _vp),
-    ]
+def _declarators(stmt, types):
+    """(name, type, is_pointer, is_const) of each declarator of `[const] TYPE [*]a, [*]b`."""
+    first, *more = (s.strip() for s in stmt.split(","))
+    m = _DECL.match(first)
+    if not m or m.group(2) not in types:
+        _fail("unknown declaration", stmt)
+    out = [(m.group(4), m.group(2), bool(m.group(3)), bool(m.group(1)))]
+    for s in more:
+        n = re.match(r"(\*?)\s*(\w+)$", s)
+        if not n:
+            _fail("unknown declaration", stmt)
+        out.append((n.group(2), m.group(2), bool(n.group(1)), out[0][3]))
+    return out
 
 
-class Seg12Args(ct.Structure):
-    _fields_ = [
-        ("num_scenes", _i64), ("scene_rows", _i64), ("chunks_per_scene", _i32),
-        ("y2", _vp), ("s2", _vp), ("t2", _vp), ("W1", _vp), ("sbias", _vp), ("Y1", _vp),
-        ("s1", _vp), ("t1", _vp), ("keep1", _vp), ("keep_scale", _f), ("W2", _vp), ("Y2", _vp),
-        ("stats", _vp),
-    ]
+def _value_type(base, pointer, opaque, text):
+    if pointer or base in opaque:
+        return ct.c_void_p
+    if base not in _SCALARS:
+        _fail("unknown type of a value", text)
+    return _SCALARS[base]
 
 
-class Conv3dGeom(ct.Structure):
-    _fields_ = [
-        ("B", _i64), ("Di", _i32), ("Hi", _i32), ("Wi", _i32), ("Do", _i32), ("Ho", _i32), ("Wo", _i32),
-        ("Cin", _i32), ("Cout", _i32), ("k", _i32), ("s", _i32), ("p", _i32), ("transposed", _i32),
-    ]
+def parse_header(text):
+    """(constants {X: int} of every PCS_X enumerator and integer define, structs {C name: [(field,
+    ctype)]}, functions [(name, restype text, [(parameter, type, is_pointer, is_const)])]) of the
+    header text.  Anything it does not understand raises ImportError naming the text."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"#ifdef __cplusplus.*?#endif", " ", text, flags=re.S)
+    consts, structs, functions, opaque = {}, {}, [], set()
+
+    def directive(m):
+        d = m.group(0).strip()
+        v = re.fullmatch(r"#define\s+PCS_(\w+)\s+(-?\d+)", d)
+        if v:
+            consts[v.group(1)] = int(v.group(2))
+        elif not re.fullmatch(r"#(ifndef\s+\w+|define\s+\w+|endif|include\s+<\w+\.h>)", d):
+            _fail("unknown directive", d)
+        return " "
+    text = re.sub(r"^[ \t]*#.*$", directive, text, flags=re.M)
+    pos, end = 0, len(text.rstrip())
+    while pos < end:
+        for kind, rx in _ITEMS:
+            m = rx.match(text, pos)
+            if m:
+                break
+        else:
+            _fail("unknown declaration", text[pos:])
+        types = _POINTEES | opaque | set(structs)
+        if kind == "opaque":
+            opaque.add(m.group(1))
+        elif kind == "struct":
+            stmts = [s for s in m.group(1).split(";") if s.strip()]
+            structs[m.group(2)] = [(name, _value_type(base, ptr, opaque, s))
+                                   for s in stmts for name, base, ptr, _ in _declarators(s, types)]
+        elif kind == "enum":
+            items = [s.strip() for s in m.group(1).split(",")]
+            for s in items[:-1] + [s for s in items[-1:] if s]:   # C allows one trailing comma
+                v = re.fullmatch(r"PCS_(\w+)\s*=\s*(-?\d+)", s)
+                if not v:
+                    _fail("enumerator without an integer value", s)
+                consts[v.group(1)] = int(v.group(2))
+        else:
+            params = [] if m.group(3).strip() in ("", "void") else m.group(3).split(",")
+            params = [_declarators(p, types)[0] for p in params]
+            for p, (_, base, ptr, _) in zip(m.group(3).split(","), params):
+                _value_type(base, ptr, opaque, p)
+            functions.append((m.group(2), " ".join(m.group(1).split()), params))
+        pos = m.end()
+    return consts, structs, functions
 
 
-class PoolBwdArgs(ct.Structure):
-    _fields_ = [
-        ("num_scenes", _i64), ("scene_rows", _i64),
-        ("Cs", _i32), ("Cg", _i32), ("col_off", _i32),
-        ("s1_alpha", _vp), ("s1_beta", _vp), ("s1_gamma", _vp),
-        ("s1_scene_s1", _vp), ("s1_scene_sum", _vp),
-        ("W_s1", _vp), ("ldw", _i64),
-        ("g", _vp), ("ysel", _vp), ("g_mean", _vp), ("g_rstd", _vp), ("g_gamma", _vp),
-        ("g_scene_sum", _vp),
-        ("dW_s1_global", _vp), ("csum", _vp),
-        ("alpha", _vp), ("beta_c", _vp), ("gamma_c", _vp),
-        ("dgamma", _vp), ("dbeta", _vp), ("dbias", _vp), ("sp", _vp),
-    ]
+def _class_name(c_name):   # pcs_pool_bwd_args -> PoolBwdArgs
+    return "".join(p.capitalize() for p in c_name.split("_")[1:])
 
 
-class HeadArgs(ct.Structure):
-    _fields_ = [
-        ("num_scenes", _i64), ("scene_rows", _i64),
-        ("Cin", _i32), ("num_classes", _i32), ("dtype", _i32), ("mode", _i32),
-        ("chunks_per_scene", _i32),
-        ("Y", _vp), ("s", _vp), ("t", _vp), ("W", _vp), ("bias", _vp), ("logits", _vp),
-        ("labels", _vp), ("class_weight", _vp), ("wsum", _vp),
-        ("dlogits", _vp), ("dl_stride_row", _i64), ("dl_stride_col", _i64),
-        ("dZ", _vp), ("mean", _vp), ("rstd", _vp), ("stats", _vp), ("wpartial", _vp),
-        ("loss_partial", _vp),
-    ]
+def _bind(structs, functions):
+    """The module's tables from a parsed header: struct classes, SIGNATURES, and per function the
+    (parameter name, C type text, tensor dtypes accepted or None, struct class or None) of call()."""
+    classes = {c: type(_class_name(c), (ct.Structure,), {"_fields_": fields, "__module__": __name__})
+               for c, fields in structs.items()}
+    restypes = {"int": ct.c_int, "int64_t": ct.c_int64, "const char *": ct.c_char_p}
+    every = [d for d in vars(torch).values() if isinstance(d, torch.dtype)]
+    byte = frozenset(d for d in every if d.itemsize == 1)   # keep bits are uint8, fp8 operands a float8 dtype
+    int8b = frozenset(d for d in every if d.itemsize == 8 and not d.is_floating_point and not d.is_complex)
+    tensors = {"float": frozenset([torch.float32]), "int32_t": frozenset([torch.int32]), "int64_t": int8b,
+               "uint64_t": int8b, "uint8_t": byte, "void": frozenset()}   # empty: any dtype
+    signatures, params = [], {}
+    for name, res, ps in functions:
+        if res not in restypes:
+            _fail("unknown return type", f"{res} {name}")
+        on_stream = any(base == "pcs_stream_t" for _, base, _, _ in ps)
+        argtypes, info = [], []
+        for pname, base, ptr, const in ps:
+            ctext = f"{'const ' if const else ''}{base}{' *' if ptr else ''}"
+            dtypes = struct = None
+            if not ptr:
+                at = _SCALARS.get(base, ct.c_void_p)   # (parse_header let only scalars and pcs_stream_t through)
+            elif base in classes:
+                at = ct.POINTER(struct := classes[base])
+            elif base == "char":
+                at = ct.c_char_p
+            elif base == "int32_t" and not const and not on_stream:   # a host out-parameter
+                at, ctext = ct.POINTER(ct.c_int32), ctext + " on the host"
+            else:
+                at, dtypes = ct.c_void_p, tensors.get(base)
+            argtypes.append(at)
+            info.append((pname, ctext, dtypes, struct))
+        signatures.append((name, restypes[res], argtypes))
+        params[name] = tuple(info)
+    return classes, signatures, params
 
 
-# (name, restype, argtypes) of every exported symbol declared in include/pcs.h
-SIGNATURES = [
-    ("pcs_gemm_geometry", _i64, [ct.POINTER(GemmArgs)]),
-    ("pcs_gemm", ct.c_int, [ct.POINTER(GemmArgs), _vp]),
-    ("pcs_conv1_fwd", ct.c_int, [ct.POINTER(GemmArgs), _vp]),
-    ("pcs_wgrad_workspace", _i64, [ct.POINTER(WgradArgs)]),
-    ("pcs_wgrad", ct.c_int, [ct.POINTER(WgradArgs), _vp]),
-    ("pcs_conv1_wgrad", ct.c_int, [ct.POINTER(WgradArgs), _vp]),
-    ("pcs_bn_fwd_finalize", ct.c_int, [_vp, _i64, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp,
-                                       _vp, _f, _f, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    ("pcs_bn_eval_coefs", ct.c_int, [_vp, _vp, _vp, _vp, _vp, _f, _i32, _vp, _vp, _vp]),
-    ("pcs_bn_bwd_finalize", ct.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
-                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    ("pcs_pool_finalize", ct.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    ("pcs_scene_gemv", ct.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
-    ("pcs_pool_bwd", ct.c_int, [ct.POINTER(PoolBwdArgs), _vp]),
-    ("pcs_head_geometry", _i64, [ct.POINTER(HeadArgs)]),
-    ("pcs_head", ct.c_int, [ct.POINTER(HeadArgs), _vp]),
-    ("pcs_ce_weight_sum", ct.c_int, [_vp, _i64, _vp, _i32, _vp, _vp, _vp]),
-    ("pcs_dropout_bits", ct.c_int, [ct.c_uint64, ct.c_uint64, _i64, _i32, _f, _vp, _vp]),
-    ("pcs_dropout_bits_bounded", ct.c_int, [ct.c_uint64, ct.c_uint64, _i64, _i32, _f, _vp, _i32, _vp]),
-    ("pcs_dropout_bits_independent", ct.c_int, [ct.c_uint64, ct.c_uint64, _i64, _i32, _f, _vp, _vp]),
-    ("pcs_reduce_partials", ct.c_int, [_vp, _i64, _i64, _f, _vp, _i64, _i64, _vp]),
-    ("pcs_reduce_partials_grouped", ct.c_int, [_vp, _i64, _i64, _i64, _f, _vp, _vp]),
-    ("pcs_cast_weight", ct.c_int, [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp]),
-    ("pcs_adam", ct.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _f, _f, _f, _f, _f, _i64, _vp]),
-    ("pcs_colstats_geometry", _i64, [_i64, _i64, _i32, ct.POINTER(_i32)]),
-    ("pcs_colstats", ct.c_int, [_vp, _i64, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp]),
-    ("pcs_bnrelu_bwd", ct.c_int, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32,
-                                  _i32, _i64, _vp, _vp]),
-    ("pcs_abi_version", ct.c_int, []),
-    ("pcs_conv3d", ct.c_int, [ct.POINTER(Conv3dGeom), _vp, _vp, _vp, _vp, _i32, _vp]),
-    ("pcs_conv3d_wgrad_workspace", _i64, [ct.POINTER(Conv3dGeom)]),
-    ("pcs_conv3d_wgrad", ct.c_int, [ct.POINTER(Conv3dGeom), _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
-    ("pcs_conv3d_weight_t", ct.c_int, [_vp, _i32, _i32, _i32, _vp, _vp]),
-    ("pcs_sparse_conv", ct.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp]),
-    ("pcs_sparse_conv_wgrad_workspace", _i64, [_i64, _i32, _i32, _i32]),
-    ("pcs_sparse_conv_wgrad", ct.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp, _vp]),
-    ("pcs_sparse_pairs_workspace", _i64, [_i64, _i32]),
-    ("pcs_sparse_pairs_count", ct.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
-    ("pcs_sparse_pairs_build", ct.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    ("pcs_sparse_conv_pairs", ct.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _i32,
-                                         _vp]),
-    ("pcs_sparse_conv_wgrad_pairs_workspace", _i64, [_vp, _i32, _i64, _i32, _i32]),
-    ("pcs_sparse_conv_wgrad_pairs", ct.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp,
-                                               _vp]),
-    ("pcs_sparse_conv_cat", ct.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp]),
-    ("pcs_sparse_conv_cat_dgrad", ct.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
-    ("pcs_sparse_conv_cat_wgrad", ct.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _vp, _vp,
-                                             _vp]),
-    ("pcs_sparse_conv_cat_pairs", ct.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp,
-                                             _i32, _i32, _vp]),
-    ("pcs_sparse_conv_cat_dgrad_pairs", ct.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32,
-                                                   _i32, _i32, _vp]),
-    ("pcs_sparse_conv_cat_wgrad_pairs", ct.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64,
-                                                   _vp, _vp, _vp]),
-    ("pcs_sparse_coarse_keys", ct.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
-    ("pcs_sparse_coarse_maps", ct.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
-    ("pcs_sparse_conv_rows", ct.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _vp]),
-    ("pcs_voxel_keys", ct.c_int, [_vp, _vp, _i64, _i64, _i32, _f, _f, _f, _f, _f, _f, _vp, _vp, _vp]),
-    ("pcs_voxel_hash_capacity", _i64, [_i64]),
-    ("pcs_voxel_hash_build", ct.c_int, [_vp, _i64, _vp, _vp, _i64, _vp]),
-    ("pcs_voxel_hash_find", ct.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp]),
-    ("pcs_sparse_neighbors", ct.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp]),
-    ("pcs_trilinear_index", ct.c_int, [_vp, _vp, _i64, _i64, _i32, _f, _f, _f, _f, _f, _f, _vp, _vp, _i64, _vp, _vp,
-                                       _vp, _vp]),
-    ("pcs_rows_interp", ct.c_int, [_vp, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _vp]),
-    ("pcs_rows_segsum", ct.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp]),
-    ("pcs_sparse_bn_geometry", _i64, [_i64, _i32, ct.POINTER(_i32)]),
-    ("pcs_sparse_bn_stats", ct.c_int, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp]),
-    ("pcs_sparse_bn_apply", ct.c_int, [_vp, _i32, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp]),
-    ("pcs_sparse_bn_bwd_reduce", ct.c_int, [_vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _vp,
-                                            _vp, _vp]),
-    ("pcs_sparse_bn_bwd_apply", ct.c_int, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
-    ("pcs_point_lift_mean", ct.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _vp]),
-    ("pcs_point_lift_bwd_workspace", _i64, [_i64, _i32, _i32]),
-    ("pcs_point_lift_mean_bwd", ct.c_int, [_vp, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64,
-                                           _vp, _vp, _vp]),
-    ("pcs_point_head_project", ct.c_int, [_vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp]),
-    ("pcs_point_head_workspace", _i64, [_i64, _i64, _i32, _i32]),
-    ("pcs_point_head_logits", ct.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
-                                         _vp]),
-    ("pcs_point_head_bwd", ct.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _vp,
-                                      _vp]),
-    ("pcs_gram_workspace", _i64, [_i64, _i64, _i32, _i32, ct.POINTER(_i32)]),
-    ("pcs_gram", ct.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
-    ("pcs_pool_rows_add", ct.c_int, [_vp, _i32, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _i32,
-                                     _vp]),
-    ("pcs_quant_fp8_rows", ct.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
-    ("pcs_gram_raw_workspace", _i64, [_i64, _i32]),
-    ("pcs_gram_raw", ct.c_int, [_vp, _i64, _i32, _i32, _vp, _i64, _vp, _vp]),
-    ("pcs_gram_wgrad", ct.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32,
-                                  _i32, _vp, _vp, _vp, _i64, _vp]),
-    ("pcs_bn_fold", ct.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
-    ("pcs_bn_s2_from_r", ct.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
-    ("pcs_bn_stats_from_gram", ct.c_int, [_vp, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp]),
-    ("pcs_bn_stats_from_gram_scenes_workspace", _i64, [_i32, _i32]),
-    ("pcs_sign_rows", ct.c_int, [_vp, _i32, _i64, _i64, _vp, _vp, _vp]),
-    ("pcs_dgrad_wgrad_folded_workspace", _i64, [ct.POINTER(WgradArgs)]),
-    ("pcs_dgrad_wgrad_folded", ct.c_int, [ct.POINTER(WgradArgs), _vp, _vp, _vp, _vp, _vp, _vp]),
-    ("pcs_bn_stats_from_gram_scenes", ct.c_int, [_vp, _vp, _i64, _vp, _i32, _i64, _i32, _i32, _i64, _vp, _i64, _vp,
-                                                 _vp]),
-    ("pcs_confusion", ct.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp]),
-    ("pcs_argmax", ct.c_int, [_vp, _i64, _i64, _i32, _vp, _vp]),
-    ("pcs_dgrad_wgrad_bn_workspace", _i64, [ct.POINTER(GemmArgs)]),
-    ("pcs_dgrad_wgrad_bn", ct.c_int, [ct.POINTER(GemmArgs), _vp, _vp, _i64, _vp]),
-    ("pcs_round_weight", ct.c_int, [_vp, _i64, _i32, _vp, _vp]),
-    ("pcs_bnrelu_bf16", ct.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
-    ("pcs_fwd_seg12_geometry", _i64, [ct.POINTER(Seg12Args)]),
-    ("pcs_fwd_seg12", ct.c_int, [ct.POINTER(Seg12Args), _vp]),
-    ("pcs_bn_stats_gram_sbias", ct.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
-    ("pcs_voxel_ids", ct.c_int, [_vp, _i64, _i32, _f, _f, _f, _f, _f, _f, _vp, _vp]),
-    ("pcs_voxelize_workspace", _i64, [_i64]),
-    ("pcs_voxelize", ct.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _f, _f, _f, _f, _f, _f, _i32, _vp, _i64,
-                                _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    ("pcs_gather_rows", ct.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp]),
-    ("pcs_voxel_padded_index", ct.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _vp]),
-    ("pcs_pad_scatter", ct.c_int, [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
-    ("pcs_last_error", ct.c_char_p, []),
-]
+if not os.path.exists(HEADER_PATH):
+    raise ImportError(f"pcs_amd reads its C ABI from {HEADER_PATH}, which is missing")
+with open(HEADER_PATH) as _f:
+    _consts, _structs, _functions = parse_header(_f.read())
+if "ABI_VERSION" not in _consts:
+    _fail("missing define", "PCS_ABI_VERSION")
+# F32, BF16, FP8, PRO_*, EPI_*, FLAG_*, HEAD_*, EINVAL, ... and ABI_VERSION (the struct layouts' version)
+globals().update(_consts)
+# GemmArgs, WgradArgs, Seg12Args, Conv3dGeom, PoolBwdArgs, HeadArgs; (name, restype, argtypes) of
+# every function the header declares
+_classes, SIGNATURES, _PARAMS = _bind(_structs, _functions)
+globals().update({c.__name__: c for c in _classes.values()})
 
 _lib = None
-
-
-# include/pcs.h PCS_ABI_VERSION: the layout of the structs mirrored in this file
-ABI_VERSION = 3
 
 
 class PcsError(RuntimeError):
@@ -255,16 +185,55 @@ def load():
         fn.restype = res
         fn.argtypes = args
     got = lib.pcs_abi_version()
-    if got != ABI_VERSION:   # the ctypes structs below mirror one layout of include/pcs.h
+    if got != ABI_VERSION:   # the struct classes mirror one layout of include/pcs.h
         raise ImportError(f"{path} has C ABI version {got}, this binding expects {ABI_VERSION}: rebuild it "
                           "(`make -C point-cloud-cnn-segmentation_amd/csrc`)")
     _lib = lib
     return lib
 
 
+_PLAIN = frozenset([int, float, type(None)])
+
+
+def _refuse(name, i, a):
+    pname, ctext, dtypes, struct = _PARAMS[name][i]
+    if isinstance(a, ct.Structure):
+        got = f"a {type(a).__name__}"
+    elif dtypes is None:
+        got = "a tensor"
+    elif dtypes and a.dtype not in dtypes:
+        got = f"a {a.dtype} tensor"
+    else:
+        got = f"a tensor on {a.device}, not on a HIP device"
+    raise TypeError(f"{name}: {pname} is {ctext}, got {got}")
+
+
+def _convert(name, args):
+    """args as the library takes them: a tensor becomes its data_ptr() once its dtype fits the
+    header's pointee type and it lives on a HIP device, a struct is passed by reference; None,
+    numbers and ctypes objects pass through."""
+    params = _PARAMS[name]
+    if len(args) != len(params):
+        raise TypeError(f"{name} takes {len(params)} arguments ({', '.join(p[0] for p in params)}), got {len(args)}")
+    out = list(args)
+    for i, a in enumerate(args):
+        if type(a) in _PLAIN:   # (first: isinstance on torch.Tensor is the slow test, and call is on the launch path)
+            continue
+        if isinstance(a, torch.Tensor):
+            dtypes = params[i][2]
+            if dtypes is None or (dtypes and a.dtype not in dtypes) or not a.is_cuda:
+                _refuse(name, i, a)
+            out[i] = a.data_ptr()
+        elif isinstance(a, ct.Structure):
+            if type(a) is not params[i][3]:
+                _refuse(name, i, a)
+            out[i] = ct.byref(a)
+    return out
+
+
 def call(name, *args):
     lib = load()
-    rc = getattr(lib, name)(*args)
+    rc = getattr(lib, name)(*_convert(name, args))
     if rc < 0:
         raise PcsError(f"{name} failed ({rc}): {lib.pcs_last_error().decode()}")
     return rc
@@ -274,10 +243,19 @@ def workspace(name, *args) -> int:
     """The value of a size query (a *_workspace, *_capacity or *_geometry function); a negative
     return raises PcsError with the library's message."""
     lib = load()
-    n = int(getattr(lib, name)(*args))
+    n = int(getattr(lib, name)(*_convert(name, args)))
     if n < 0:
         raise PcsError(lib.pcs_last_error().decode())
     return n
+
+
+def dtype_code(dtype, what=None):
+    """BF16 / F32 of a storage dtype; ``what`` names the argument in the error."""
+    if dtype == torch.bfloat16:
+        return BF16
+    if dtype == torch.float32:
+        return F32
+    raise ValueError(f"{what} must be bf16 or fp32, got {dtype}" if what else f"bf16 or fp32 expected, got {dtype}")
 
 
 def ptr(t):

@@ -69,5 +69,5 @@ def predict(model, points):
     B, N, C = logits.shape
     out = torch.empty(B, N, dtype=torch.int64, device=logits.device)
     z = logits.reshape(B * N, C)
-    L.call("pcs_argmax", L.ptr(z), z.stride(0), B * N, C, L.ptr(out), L.stream_ptr())
+    L.call("pcs_argmax", z, z.stride(0), B * N, C, out, L.stream_ptr())
     return out

@@ -203,11 +203,6 @@ def _f32(dev, *shape):
     return torch.empty(*shape, dtype=torch.float32, device=dev)
 
 
-def _call(name, *args):
-    """_lib.call with tensors passed as their device pointers (None = NULL)."""
-    return L.call(name, *(a.data_ptr() if torch.is_tensor(a) else a for a in args))
-
-
 def _struct(cls, **members):
     """A C-ABI argument struct; members given as tensors become device pointers (None = NULL)."""
     a = cls()
@@ -292,10 +287,10 @@ class Engine:
     def _launch(self, tag, name, *args):
         """C-ABI call, bracketed by HIP events on the launch stream when timing is on."""
         if self.timing is None or tag is None or (self.timing_tags is not None and tag not in self.timing_tags):
-            return _call(name, *args)
+            return L.call(name, *args)
         st, en = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         st.record()
-        r = _call(name, *args)
+        r = L.call(name, *args)
         en.record()
         self.timing.setdefault(tag, []).append((st, en))
         return r
@@ -324,7 +319,7 @@ class Engine:
         key = (B, N, K, ncols, pro, epi, flags, dtype)
         if key not in self._geo:
             a = self._gemm_args(B, N, K, ncols, dtype, pro, epi, 0, flags)
-            rpc = L.workspace("pcs_gemm_geometry", ct.byref(a))
+            rpc = L.workspace("pcs_gemm_geometry", a)
             self._geo[key] = (a.chunks_per_scene, rpc)
         return self._geo[key]
 
@@ -344,7 +339,7 @@ class Engine:
             cols = 64 if conv == "seg_conv1" else ld     # seg_conv1: local half only
             Wc = self._empty(rows, cols, device=dev)
             WcT = self._empty(cols, rows, device=dev)
-            _call("pcs_cast_weight", W, rows, cols, ld, self.dt, Wc, WcT, s)
+            L.call("pcs_cast_weight", W, rows, cols, ld, self.dt, Wc, WcT, s)
             wc[conv] = (Wc, WcT)
         if self.fp8:
             wc["global_feat_fp8"] = self._quant_fp8(P["global_feat.weight"])
@@ -358,7 +353,7 @@ class Engine:
         Wq = torch.empty(rows, cols, dtype=torch.uint8, device=dev)
         sc = torch.empty(rows, dtype=torch.uint8, device=dev)
         deq = _f32(dev, rows, cols)
-        _call("pcs_quant_fp8_rows", W, rows, cols, W.stride(0), Wq, sc, deq, L.stream_ptr())
+        L.call("pcs_quant_fp8_rows", W, rows, cols, W.stride(0), Wq, sc, deq, L.stream_ptr())
         return Wq, sc, deq
 
     def _bn_finalize(self, P, bufs, sv, bnname, stats, C, cps, rpc, offset=None):
@@ -369,11 +364,11 @@ class Engine:
         if sv.train:
             rm, rv = bufs.get(f"{bnname}.running_mean"), bufs.get(f"{bnname}.running_var")
             upd = int(rm is not None and rv is not None)
-            _call("pcs_bn_fwd_finalize", stats, B, N, C, cps, rpc, g, b, offset, rm, rv, BN_MOMENTUM, BN_EPS, upd,
-                  coef.mean, coef.rstd, coef.scale, coef.shift, coef.scene_sum, L.stream_ptr())
+            L.call("pcs_bn_fwd_finalize", stats, B, N, C, cps, rpc, g, b, offset, rm, rv, BN_MOMENTUM, BN_EPS, upd,
+                   coef.mean, coef.rstd, coef.scale, coef.shift, coef.scene_sum, L.stream_ptr())
         else:
-            _call("pcs_bn_eval_coefs", g, b, bufs[f"{bnname}.running_mean"], bufs[f"{bnname}.running_var"], offset,
-                  BN_EPS, C, coef.scale, coef.shift, L.stream_ptr())
+            L.call("pcs_bn_eval_coefs", g, b, bufs[f"{bnname}.running_mean"], bufs[f"{bnname}.running_var"], offset,
+                   BN_EPS, C, coef.scale, coef.shift, L.stream_ptr())
         return coef
 
     def _gemm(self, sv, K, ncols, pro, epi, A, W, C, *, tag=None, dtype=None, extra_flags=0, **fields):
@@ -384,7 +379,7 @@ class Engine:
         fields.setdefault("a_keep_scale", 1.0)
         fields.setdefault("c_keep_scale", 1.0)
         a = self._gemm_args(sv.B, sv.N, K, ncols, dtype, pro, epi, cps, flags | extra_flags, A=A, W=W, C=C, **fields)
-        self._launch(tag, "pcs_gemm", ct.byref(a), L.stream_ptr())
+        self._launch(tag, "pcs_gemm", a, L.stream_ptr())
 
     def _wgrad_args(self, sv, cout, cin, dy_mode, x_mode, dW, ldw=0, x_keep_scale=1.0, **members):
         return _struct(L.WgradArgs, num_scenes=sv.B, scene_rows=sv.N, Cout=cout, Cin=cin, dtype=self.dt, dy_mode=dy_mode,
@@ -396,10 +391,10 @@ class Engine:
             a.splits_per_scene = max(1, min((1024 + sv.B - 1) // sv.B, (sv.N + 255) // 256))
             nbytes = sv.B * a.splits_per_scene * cout * cin * 4
         else:
-            nbytes = L.workspace("pcs_wgrad_workspace", ct.byref(a))
+            nbytes = L.workspace("pcs_wgrad_workspace", a)
         ws = _f32(dW.device, max(nbytes // 4, 1))
         a.partial = ws.data_ptr()
-        self._launch(tag, "pcs_conv1_wgrad" if conv1 else "pcs_wgrad", ct.byref(a), L.stream_ptr())
+        self._launch(tag, "pcs_conv1_wgrad" if conv1 else "pcs_wgrad", a, L.stream_ptr())
         return ws  # keep alive until the stream consumes it (caching allocator is stream-ordered)
 
     def _rounded(self, W):
@@ -407,7 +402,7 @@ class Engine:
         if self.dt == L.F32:
             return W
         out = torch.empty_like(W)
-        _call("pcs_round_weight", W, W.numel(), self.dt, out, L.stream_ptr())
+        L.call("pcs_round_weight", W, W.numel(), self.dt, out, L.stream_ptr())
         return out
 
     def _gram(self, Y, s_, t_, B, N, C, tag=None):
@@ -483,9 +478,9 @@ class Engine:
             ss = L.stream_ptr()
             for i, (m, width) in enumerate(((m1, 512), (m2, 256))):
                 if self.dropout_draw == "independent":
-                    _call("pcs_dropout_bits_independent", seed, i, M, width, DROPOUT_P, m, ss)
+                    L.call("pcs_dropout_bits_independent", seed, i, M, width, DROPOUT_P, m, ss)
                 else:
-                    _call("pcs_dropout_bits_bounded", seed, i, M, width, DROPOUT_P, m, max_wg, ss)
+                    L.call("pcs_dropout_bits_bounded", seed, i, M, width, DROPOUT_P, m, max_wg, ss)
             sv.mask_ready = torch.cuda.Event()
             sv.mask_ready.record(side)
         m1.record_stream(side)
@@ -501,7 +496,7 @@ class Engine:
         _, _, M, dev, s = self._dims(sv)
         out = self._empty(M, 2 * K if split else K, device=dev)
         c = sv.bn[bn]
-        _call("pcs_bnrelu_bf16", sv.ys[conv], M, K, c.scale, c.shift, int(split), out, s)
+        L.call("pcs_bnrelu_bf16", sv.ys[conv], M, K, c.scale, c.shift, int(split), out, s)
         return out
 
     def _layer(self, P, bufs, sv, conv, src, offset=None, A_raw=None, K=None, **kw):
@@ -533,11 +528,11 @@ class Engine:
         # conv1 (K=4), on the generic 128-row geometry
         y1 = self._empty(M, 64, device=dev, dtype=torch.float32 if pt.trunk32 else None)
         a = self._gemm_args(B, N, D, 64, L.F32, flags=L.FLAG_GENERIC)
-        rpc, cps = L.workspace("pcs_gemm_geometry", ct.byref(a)), a.chunks_per_scene
+        rpc, cps = L.workspace("pcs_gemm_geometry", a), a.chunks_per_scene
         st = _f32(dev, B * cps, 64, 2) if train else None
         a = self._gemm_args(B, N, D, 64, L.F32 if pt.trunk32 else self.dt, cps=cps, A=sv.x,
                             W=P["conv1.weight"], C=y1, bias=None, stats=st)
-        self._launch("fwd:conv1", "pcs_conv1_fwd", ct.byref(a), s)
+        self._launch("fwd:conv1", "pcs_conv1_fwd", a, s)
         sv.ys["conv1"] = y1
         sv.bn["bn1"] = self._bn_finalize(P, bufs, sv, "bn1", st, 64, cps, rpc, P["conv1.bias"])
         tkw = {"dtype": L.F32} if pt.trunk32 else {}
@@ -560,7 +555,7 @@ class Engine:
             c4 = sv.bn["bn4"]
             sv.gram4 = self._gram(sv.ys["conv4"], c4.scale, c4.shift, B, N, 128, tag="fwd_stats:conv5")
             st, cps, rpc = _f32(dev, B, 1024, 2), 1, N
-            _call("pcs_bn_stats_from_gram", sv.gram4[0], sv.gram4[1], M, W5, self.dt, 128, 1024, 128, B, st, s)
+            L.call("pcs_bn_stats_from_gram", sv.gram4[0], sv.gram4[1], M, W5, self.dt, 128, 1024, 128, B, st, s)
         elif train:
             st, cps, rpc = self._stats_buf(sv, 128, 1024)
             self._gemm(sv, 128, 1024, L.PRO_BNRELU, L.EPI_FWD, sv.ys["conv4"], W5, None,
@@ -606,7 +601,7 @@ class Engine:
         gws = self._gram_raw(a5, G5, beside=(lambda: self._draw_masks(sv, seed, max_wg)) if pt.draw_beside_gram else None)
         # per-scene column sums of a5 from conv5's per-chunk partials (chunks are scene-aligned)
         live["Sb2"] = Sb2 = _f32(dev, B, 1024, 2)
-        _call("pcs_reduce_partials_grouped", sv.a5_colsum, B, sv.a5_colsum.shape[0] // B, 2048, 1.0, Sb2, s)
+        L.call("pcs_reduce_partials_grouped", sv.a5_colsum, B, sv.a5_colsum.shape[0] // B, 2048, 1.0, Sb2, s)
         Sb = Sb2[..., 0].contiguous()
         live["stats"] = st = _f32(dev, B, 1024, 2)
         qbytes = L.workspace("pcs_bn_stats_from_gram_scenes_workspace", 1024, 1024)
@@ -639,7 +634,7 @@ class Engine:
             Wf, kw = wc["global_feat_fp8"][0], dict(w_scale=wc["global_feat_fp8"][1], extra_flags=L.FLAG_AW_FP8)
         if st_g is None and pt.glds:
             live["Wsg"] = Wsg = torch.empty_like(Wf)
-            _call("pcs_sign_rows", Wf, self.a5_dt, 1024, 1024, gamma_g, Wsg, s)
+            L.call("pcs_sign_rows", Wf, self.a5_dt, 1024, 1024, gamma_g, Wsg, s)
             Wf, kw["extra_flags"] = Wsg, kw["extra_flags"] | L.FLAG_POOL_SIGNED_W
         self._gemm(sv, 1024, 1024, L.PRO_RAW, L.EPI_FWD, a5, Wf, None, stats=st_g, pool=pool, es=gamma_g,
                    tag="fwd:global_feat", **kw)
@@ -648,7 +643,7 @@ class Engine:
         sv.g = _f32(dev, B, 1024)
         sv.am = torch.empty(B, 1024, dtype=torch.int32, device=dev)
         sv.ysel = _f32(dev, B, 1024)
-        _call("pcs_pool_finalize", pool, B, N, 1024, cps_g, cg.scale, cg.shift, sv.g, sv.am, sv.ysel, s)
+        L.call("pcs_pool_finalize", pool, B, N, 1024, cps_g, cg.scale, cg.shift, sv.g, sv.am, sv.ysel, s)
         if self.record_pool_rows:              # test hooks: the max-pool's rows
             self.last_pool_rows = sv.am.clone()
         if self.pool_rows_override is not None:
@@ -680,7 +675,7 @@ class Engine:
         sbias = _f32(dev, B, 512)
         live["soff"] = soff = _f32(dev, 512)
         Ws1 = P["seg_conv1.weight"]
-        _call("pcs_scene_gemv", sv.g, B, 1024, Ws1, Ws1.shape[1], 64, P["seg_conv1.bias"], 512, sbias, soff, s)
+        L.call("pcs_scene_gemv", sv.g, B, 1024, Ws1, Ws1.shape[1], 64, P["seg_conv1.bias"], 512, sbias, soff, s)
         sv.sbias_s1 = sbias   # the stored Y'_seg1 = a2 W_l^T + sbias[b] (the folded backward)
         if not pt.fused12:    # (fused: with seg_conv2 below, pcs_fwd_seg12)
             self._layer(P, bufs, sv, "seg_conv1", "conv2", soff, K=64, scene_bias=sbias,
@@ -702,24 +697,24 @@ class Engine:
         rec = 64 * 64 + 64
         cps3 = sv.gram2.shape[0] // B
         per_scene = _f32(dev, B, rec)
-        _call("pcs_reduce_partials_grouped", sv.gram2, B, cps3, rec, 1.0, per_scene, s)
+        L.call("pcs_reduce_partials_grouped", sv.gram2, B, cps3, rec, 1.0, per_scene, s)
         tot = _f32(dev, rec)
-        _call("pcs_reduce_partials", per_scene, B, rec, 1.0, tot, 1, rec, s)
+        L.call("pcs_reduce_partials", per_scene, B, rec, 1.0, tot, 1, rec, s)
         G2 = tot[:64 * 64]
         Sb = per_scene[:, 64 * 64:].contiguous()
         Ws1 = P["seg_conv1.weight"]
         Ws1_r = self._rounded(Ws1)
         st1 = _f32(dev, B, 512, 2)
-        _call("pcs_bn_stats_gram_sbias", G2, Sb, B, N, Ws1_r, Ws1.shape[1], 64, 512, sbias, st1, s)
+        L.call("pcs_bn_stats_gram_sbias", G2, Sb, B, N, Ws1_r, Ws1.shape[1], 64, 512, sbias, st1, s)
         sv.bn["bn_seg1"] = c1 = self._bn_finalize(P, bufs, sv, "bn_seg1", st1, 512, 1, N, soff)
         y1, y2 = self._empty(M, 512, device=dev), self._empty(M, 256, device=dev)
         a = _struct(L.Seg12Args, num_scenes=B, scene_rows=N, y2=sv.ys["conv2"], s2=c2.scale, t2=c2.shift,
                     W1=wc["seg_conv1"][0], sbias=sbias, Y1=y1, s1=c1.scale, t1=c1.shift, keep1=m1, keep_scale=keep,
                     W2=wc["seg_conv2"][0], Y2=y2)
-        rpc, cps = L.workspace("pcs_fwd_seg12_geometry", ct.byref(a)), a.chunks_per_scene
+        rpc, cps = L.workspace("pcs_fwd_seg12_geometry", a), a.chunks_per_scene
         st2 = _f32(dev, B * cps, 256, 2)
         a.stats = L.ptr(st2)
-        self._launch("fwd:seg_conv1+2", "pcs_fwd_seg12", ct.byref(a), s)
+        self._launch("fwd:seg_conv1+2", "pcs_fwd_seg12", a, s)
         sv.ys["seg_conv1"], sv.ys["seg_conv2"] = y1, y2
         sv.bn["bn_seg2"] = self._bn_finalize(P, bufs, sv, "bn_seg2", st2, 256, cps, rpc, P["seg_conv2.bias"])
 
@@ -732,7 +727,7 @@ class Engine:
                      logits=sv.logits if mode != L.HEAD_BWD else None)
         hb = None
         if mode != L.HEAD_FWD:
-            L.workspace("pcs_head_geometry", ct.byref(ha))
+            L.workspace("pcs_head_geometry", ha)
             nch = B * ha.chunks_per_scene
             hb = dict(dZ=torch.empty(B * N * 1024, dtype=self.tdt, device=dev), stats=_f32(dev, nch, 128, 2),
                       wpartial=_f32(dev, nch, self.C * 129), loss_partial=_f32(dev, nch), cps=ha.chunks_per_scene,
@@ -749,7 +744,7 @@ class Engine:
             ha.dlogits = L.ptr(dl)
             ha.dl_stride_row, ha.dl_stride_col = dl.stride(0), dl.stride(1)
             hb["dl"] = dl
-        self._launch(f"head:{mode}", "pcs_head", ct.byref(ha), s)
+        self._launch(f"head:{mode}", "pcs_head", ha, s)
         return hb
 
     # ------------------------------------------------------------------ backward
@@ -781,8 +776,8 @@ class Engine:
         fc = sv.bn[bnname]
         C = fc.mean.shape[0]
         al, be, ga = (_f32(dev, C) for _ in range(3))
-        _call("pcs_bn_bwd_finalize", stats, B, N, C, cps, fc.mean, fc.rstd, P[f"{bnname}.weight"], fc.scene_sum, al, be,
-              ga, bw.G(f"{bnname}.weight"), bw.G(f"{bnname}.bias"), bw.G(f"{conv}.bias"), scene_s1, s)
+        L.call("pcs_bn_bwd_finalize", stats, B, N, C, cps, fc.mean, fc.rstd, P[f"{bnname}.weight"], fc.scene_sum, al,
+               be, ga, bw.G(f"{bnname}.weight"), bw.G(f"{bnname}.bias"), bw.G(f"{conv}.bias"), scene_s1, s)
         bw.coefs[bnname] = (al, be, ga)
 
     def _wgrad_bn(self, sv, bw, conv, dz, prev, x_mask=None, cin=None, ldw=0):
@@ -816,7 +811,7 @@ class Engine:
             st = _f32(dev, B * cps, cin, 2)
             ws = _f32(dev, nbytes // 4)
             a.stats = L.ptr(st)
-            self._launch(f"dgrad+wgrad:{conv}", "pcs_dgrad_wgrad_bn", ct.byref(a), ws, bw.G(f"{conv}.weight"), 0, s)
+            self._launch(f"dgrad+wgrad:{conv}", "pcs_dgrad_wgrad_bn", a, ws, bw.G(f"{conv}.weight"), 0, s)
             bw.keep.append(ws)
         else:
             cps, _ = self.geometry(B, N, cout, cin, L.PRO_BWD, L.EPI_DGRAD, flags=pt.flags)
@@ -834,8 +829,8 @@ class Engine:
         _, _, M, dev, s = self._dims(sv)
         m1, m2 = sv.masks
         # seg_conv4: weight and bias are adjacent in the flat buffer
-        _call("pcs_reduce_partials", hb["wpartial"], hb["nch"], self.C * 129, 1.0, bw.G("seg_conv4.weight"),
-              self.C * 129, self.C * 129, s)
+        L.call("pcs_reduce_partials", hb["wpartial"], hb["nch"], self.C * 129, 1.0, bw.G("seg_conv4.weight"),
+               self.C * 129, self.C * 129, s)
         self._bn_bwd(P, sv, bw, "bn_seg3", "seg_conv3", hb["stats"], hb["cps"])
         bw.bufB = torch.empty(M * 1024, dtype=self.tdt, device=dev)
         self._bwd_layer(P, sv, bw, "seg_conv3", bw.bufA, "seg_conv2", bw.bufB, c_mask=m2)
@@ -857,7 +852,7 @@ class Engine:
                      g_gamma=P["bn_global.weight"], g_scene_sum=cg.scene_sum, dW_s1_global=bw.G("seg_conv1.weight"),
                      csum=csum, alpha=ag, beta_c=bg, gamma_c=gg, dgamma=bw.G("bn_global.weight"),
                      dbeta=bw.G("bn_global.bias"), dbias=bw.G("global_feat.bias"), sp=sp)
-        _call("pcs_pool_bwd", ct.byref(pa), s)
+        L.call("pcs_pool_bwd", pa, s)
         bw.keep.append(csum)
         return sp
 
@@ -882,13 +877,13 @@ class Engine:
         Ws1_r = self._rounded(Ws1)     # the W_l the forward GEMM used
         WaT, Hs1 = self._empty(64, 512, device=dev), self._empty(64, 64, device=dev)
         # no cvec output: the folded kernel forms its per-scene cvec_b itself (folded_cvec_kernel)
-        _call("pcs_bn_fold", Ws1_r, 512, 64, Ws1.shape[1], a1, b1, g1, self.dt, WaT, None, Hs1, s)
+        L.call("pcs_bn_fold", Ws1_r, 512, 64, Ws1.shape[1], a1, b1, g1, self.dt, WaT, None, Hs1, s)
         fa = self._wgrad_args(sv, 512, 64, L.PRO_RAW, L.PRO_BNRELU, bw.G("seg_conv1.weight"), ldw=Ws1.shape[1],
                               dZ=dz_s1, alpha=a1, beta=b1, gamma=g1, X=ys["conv2"], s=p2.scale, t=p2.shift)
-        nbytes = L.workspace("pcs_dgrad_wgrad_folded_workspace", ct.byref(fa))
+        nbytes = L.workspace("pcs_dgrad_wgrad_folded_workspace", fa)
         ws1 = _f32(dev, nbytes // 4)
         fa.partial = ws1.data_ptr()
-        self._launch("dgrad+wgrad:seg_conv1", "pcs_dgrad_wgrad_folded", ct.byref(fa), WaT, Hs1, Ws1_r, sv.sbias_s1, dA2, s)
+        self._launch("dgrad+wgrad:seg_conv1", "pcs_dgrad_wgrad_folded", fa, WaT, Hs1, Ws1_r, sv.sbias_s1, dA2, s)
         bw.keep.append((ws1, Ws1_r, WaT, Hs1))
         return dA2
 
@@ -908,7 +903,8 @@ class Engine:
         cvec = _f32(dev, 1024)
         # fp8: H in fp32, then e4m3 rows with one scale each (H is symmetric: row n = column n)
         Hg = _f32(dev, 1024, 1024) if pt.fp8 else self._empty(1024, 1024, device=dev)
-        _call("pcs_bn_fold", Wg_r, 1024, 1024, Wg_r.shape[1], None, bg, gg, L.F32 if pt.fp8 else self.dt, None, cvec, Hg, s)
+        L.call("pcs_bn_fold", Wg_r, 1024, 1024, Wg_r.shape[1], None, bg, gg, L.F32 if pt.fp8 else self.dt, None, cvec, Hg,
+               s)
         pool_rows = dict(pool_idx=sv.am, pool_coef=sp, pool_w=Wg_r, pool_ldw=Wg_r.shape[1], pool_c=1024)
         if pt.fp8:
             Hq, hsc, _ = self._quant_fp8(Hg)   # (the dequantized copy lives until `_` is next assigned)
@@ -924,8 +920,8 @@ class Engine:
                    tag="dgrad:global_feat", **kw)
         if pt.fp8 or pt.glds:
             # the max-pool rows' sparse term, with the W the forward GEMM used; S1 in both
-            _call("pcs_pool_rows_add", dz5, self.dt, a5, self.a5_dt, B, N, 1024, sv.am, sp, Wg_r, Wg_r.shape[1], 1024,
-                  st5, cps5, s)
+            L.call("pcs_pool_rows_add", dz5, self.dt, a5, self.a5_dt, B, N, 1024, sv.am, sp, Wg_r, Wg_r.shape[1], 1024,
+                   st5, cps5, s)
         if self.perturb is not None and "dz5" in self.perturb:   # test hooks
             c0, c1, scale = self.perturb["dz5"]
             dz5.view(M, 1024)[:, c0:c1].mul_(scale)
@@ -950,12 +946,12 @@ class Engine:
             # computed in the forward (bn_global's statistics); S = sum of the per-scene sums
             gram, Sb, ws = sv.gram5
             colsum = _f32(dev, 1024)
-            _call("pcs_reduce_partials", Sb, B, 1024, 1.0, colsum, 1024, 1024, s)
+            L.call("pcs_reduce_partials", Sb, B, 1024, 1.0, colsum, 1024, 1024, s)
         elif raw:
             # a5 is the activation itself: LDS-DMA Gram; S from conv5's per-chunk column sums
             ws = self._gram_raw(a5, gram)
             cs2 = _f32(dev, 1024, 2)
-            _call("pcs_reduce_partials", sv.a5_colsum, sv.a5_colsum.shape[0], 2048, 1.0, cs2, 2048, 2048, s)
+            L.call("pcs_reduce_partials", sv.a5_colsum, sv.a5_colsum.shape[0], 2048, 1.0, cs2, 2048, 2048, s)
             colsum = cs2[:, 0].contiguous()
             bw.keep.append(cs2)
         else:
@@ -979,12 +975,12 @@ class Engine:
                                    dZ=dz5, X=y4, s=pc4.scale, t=pc4.shift))
         if cap is not None:
             cap.update(r5=r5.clone(), y4=y4, s4=pc4.scale, t4=pc4.shift)
-        _call("pcs_bn_s2_from_r", st5, B * cps5, 1024, r5, sv.wc["conv5"][0], self.dt, 128, 128, pc5.mean, pc5.rstd, s)
+        L.call("pcs_bn_s2_from_r", st5, B * cps5, 1024, r5, sv.wc["conv5"][0], self.dt, 128, 128, pc5.mean, pc5.rstd, s)
         self._bn_bwd(P, sv, bw, "bn5", "conv5", st5, cps5)
         al5, be5, ga5 = bw.coefs["bn5"]
         W5_r = self._rounded(P["conv5.weight"])
         ws_t, c5, h4 = self._empty(128, 1024, device=dev), _f32(dev, 128), self._empty(128, 128, device=dev)
-        _call("pcs_bn_fold", W5_r, 1024, 128, 128, al5, be5, ga5, self.dt, ws_t, c5, h4, s)
+        L.call("pcs_bn_fold", W5_r, 1024, 128, 128, al5, be5, ga5, self.dt, ws_t, c5, h4, s)
         # one pass: [dz5 | a4] [Ws ; H4] + c5 (PCS_PRO_CAT), then bn4's ReLU mask and S1 / S2
         cps4, _ = self.geometry(B, N, 1024 + 128, 128, L.PRO_CAT, L.EPI_DGRAD, flags=sv.paths.flags)
         bw.st = _f32(dev, B * cps4, 128, 2)

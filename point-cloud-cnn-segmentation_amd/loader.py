@@ -62,8 +62,8 @@ def pad_on_device(rb: RaggedBatch, device=None, scene_rows: int | None = None, s
         points = torch.empty(B, N, 4, dtype=torch.float32, device=device)
         labels = torch.empty(B, N, dtype=torch.int64, device=device)
         masks = torch.empty(B, N, dtype=torch.bool, device=device)
-        L.call("pcs_pad_scatter", L.ptr(pts_d), L.ptr(lab_d), lab_d.element_size(), L.ptr(off_d), B, N,
-               L.ptr(points), L.ptr(labels), L.ptr(masks), L.stream_ptr(device))
+        L.call("pcs_pad_scatter", pts_d, lab_d, lab_d.element_size(), off_d, B, N, points, labels, masks,
+               L.stream_ptr(device))
     return points, labels, masks
 
 

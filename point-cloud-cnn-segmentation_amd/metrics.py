@@ -40,8 +40,7 @@ class ConfusionMeter:
             y = y.long().contiguous()
         if y.numel() != z.shape[0]:
             raise ValueError(f"{y.numel()} labels for {z.shape[0]} logit rows")
-        L.call("pcs_confusion", L.ptr(z), z.stride(0), L.ptr(y), y.numel(), self.C, L.ptr(self.cm),
-               L.stream_ptr())
+        L.call("pcs_confusion", z, z.stride(0), y, y.numel(), self.C, self.cm, L.stream_ptr())
         return self
 
     def compute(self) -> dict:

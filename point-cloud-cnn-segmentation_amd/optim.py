@@ -87,9 +87,9 @@ class FusedAdam(torch.optim.Optimizer):
         self.step_count += 1
         grp = self.param_groups[0]
         b1, b2 = grp["betas"]
-        L.call("pcs_adam", L.ptr(pflat), L.ptr(gflat), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-               pflat.numel(), L.ptr(self.grad_scale), float(grp["lr"]), float(b1), float(b2),
-               float(grp["eps"]), float(grp["weight_decay"]), self.step_count, L.stream_ptr())
+        L.call("pcs_adam", pflat, gflat, self.exp_avg, self.exp_avg_sq, pflat.numel(), self.grad_scale,
+               float(grp["lr"]), float(b1), float(b2), float(grp["eps"]), float(grp["weight_decay"]), self.step_count,
+               L.stream_ptr())
         return loss
 
     def zero_grad(self, set_to_none: bool = False):

@@ -26,7 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib as L
-from .pointvoxel import PV_CH_ALIGN, PointVoxelMap, _code, _cut, _rows_in, devoxelize
+from .pointvoxel import PV_CH_ALIGN, PointVoxelMap, _cut, _rows_in, devoxelize
 from .voxel import _pad_channels
 
 MAX_CIN = 8        # point columns of the lift kernel
@@ -67,8 +67,8 @@ class _PointLiftMeanFn(torch.autograd.Function):
             return torch.zeros(V, C, dtype=out_dtype, device=dev)
         order, seg_off, _, inv, _ = pvm.points_by_voxel()
         y = torch.empty(V, ck, dtype=out_dtype, device=dev)
-        L.call("pcs_point_lift_mean", L.ptr(points), points.shape[1], cin, L.ptr(wk), L.ptr(bk), L.ptr(order),
-               L.ptr(seg_off), L.ptr(inv), V, ck, L.ptr(y), _code(out_dtype), L.stream_ptr(dev))
+        L.call("pcs_point_lift_mean", points, points.shape[1], cin, wk, bk, order, seg_off, inv, V, ck, y,
+               L.dtype_code(out_dtype), L.stream_ptr(dev))
         return _cut(y, C)
 
     @staticmethod
@@ -86,9 +86,8 @@ class _PointLiftMeanFn(torch.autograd.Function):
         ws = _workspace(nbytes, dev)
         dw = torch.empty(ck, cin, device=dev)
         db = torch.empty(ck, device=dev) if want_b else None
-        L.call("pcs_point_lift_mean_bwd", L.ptr(dk), _code(dk.dtype), L.ptr(points), points.shape[1], cin, L.ptr(wk),
-               L.ptr(bk), L.ptr(order), L.ptr(seg_off), L.ptr(inv), V, ck, L.ptr(ws), nbytes, L.ptr(dw), L.ptr(db),
-               L.stream_ptr(dev))
+        L.call("pcs_point_lift_mean_bwd", dk, L.dtype_code(dk.dtype), points, points.shape[1], cin, wk, bk, order,
+               seg_off, inv, V, ck, ws, nbytes, dw, db, L.stream_ptr(dev))
         return dw[:C], (db[:C] if want_b else None), None, None, None
 
 
@@ -108,7 +107,7 @@ def point_lift_mean(points: torch.Tensor, weight: torch.Tensor, bias, pvm: Point
                          f"{list(points.shape)}")
     if bias is not None and tuple(bias.shape) != (weight.shape[0],):
         raise ValueError(f"point_lift_mean: bias must be [{weight.shape[0]}], got {list(bias.shape)}")
-    _code(out_dtype)
+    L.dtype_code(out_dtype)
     return _PointLiftMeanFn.apply(weight, bias, points.detach().float().contiguous(), pvm, out_dtype)
 
 
@@ -128,8 +127,7 @@ def _project(xk, wk):
     if V == 0:
         return torch.zeros(1, K, device=xk.device)
     z = torch.empty(V, K, device=xk.device)
-    L.call("pcs_point_head_project", L.ptr(xk), _code(xk.dtype), V, xk.shape[1], L.ptr(wk), K, L.ptr(z),
-           L.stream_ptr(xk.device))
+    L.call("pcs_point_head_project", xk, L.dtype_code(xk.dtype), V, xk.shape[1], wk, K, z, L.stream_ptr(xk.device))
     return z
 
 
@@ -143,8 +141,8 @@ def _head_bwd(dl, pvm, xk, wk, gscale, want_dx, want_dw):
     ws = _workspace(nbytes, dev)
     dx = torch.empty_like(xk) if want_dx else None
     dw = torch.empty_like(wk) if want_dw else None
-    L.call("pcs_point_head_bwd", L.ptr(dl), L.ptr(point), L.ptr(w), L.ptr(seg_off), L.ptr(xk), _code(xk.dtype), V, ck,
-           L.ptr(wk), K, L.ptr(gscale), L.ptr(dx), L.ptr(ws), nbytes, L.ptr(dw), L.stream_ptr(dev))
+    L.call("pcs_point_head_bwd", dl, point, w, seg_off, xk, L.dtype_code(xk.dtype), V, ck, wk, K, gscale, dx, ws,
+           nbytes, dw, L.stream_ptr(dev))
     return dx, dw
 
 
@@ -160,8 +158,8 @@ class _PointHeadFn(torch.autograd.Function):
         logits = torch.empty(T, K, device=dev)
         if T > 0:
             z = _project(xk, wk)
-            L.call("pcs_point_head_logits", L.ptr(z), L.ptr(pvm.corner), L.ptr(pvm.weight), T, K, L.ptr(bk), None, None,
-                   None, L.ptr(logits), None, None, 0, None, None, L.stream_ptr(dev))
+            L.call("pcs_point_head_logits", z, pvm.corner, pvm.weight, T, K, bk, None, None, None, logits, None, None,
+                   0, None, None, L.stream_ptr(dev))
         return logits
 
     @staticmethod
@@ -185,7 +183,7 @@ class _PointHeadLossFn(torch.autograd.Function):
         s = L.stream_ptr(dev)
         counts = torch.empty(K, dtype=torch.int64, device=dev)
         wsum = torch.empty(4, device=dev)   # [sum of class_weight[label], valid labels, 1 / sum, -]
-        L.call("pcs_ce_weight_sum", L.ptr(labels), T, L.ptr(class_weight), K, L.ptr(counts), L.ptr(wsum), s)
+        L.call("pcs_ce_weight_sum", labels, T, class_weight, K, counts, wsum, s)
         want = ctx.needs_input_grad[:3]
         want_b = bias is not None and want[2]
         dl = torch.empty(T, K, device=dev) if (want[0] or want[1]) else None
@@ -195,9 +193,8 @@ class _PointHeadLossFn(torch.autograd.Function):
         nbytes = L.workspace("pcs_point_head_workspace", T, V, xk.shape[1], K)
         ws = _workspace(nbytes, dev)
         z = _project(xk, wk)
-        L.call("pcs_point_head_logits", L.ptr(z), L.ptr(pvm.corner), L.ptr(pvm.weight), T, K, L.ptr(bk), L.ptr(labels),
-               L.ptr(class_weight), wsum[2:].data_ptr(), L.ptr(logits), L.ptr(dl), L.ptr(ws), nbytes, L.ptr(loss),
-               L.ptr(db), s)
+        L.call("pcs_point_head_logits", z, pvm.corner, pvm.weight, T, K, bk, labels, class_weight, wsum[2:], logits, dl,
+               ws, nbytes, loss, db, s)
         ctx.pvm, ctx.cfg = pvm, (x.shape[1], x.dtype)
         ctx.save_for_backward(xk, wk, dl, db)
         if return_logits:

@@ -97,18 +97,9 @@ def point_voxel_map(rb: RaggedBatch, sv: SparseVoxels, lo=(-1.0, -1.0, -1.0), hi
     own = torch.empty(T, dtype=torch.int32, device=dev)
     corner = torch.empty(T, CORNERS, dtype=torch.int32, device=dev)
     weight = torch.empty(T, CORNERS, dtype=torch.float32, device=dev)
-    L.call("pcs_trilinear_index", L.ptr(pts), L.ptr(off), off.numel() - 1, T, int(sv.grid), *_box(lo, hi),
-           L.ptr(sv.table_keys), L.ptr(sv.table_vals), sv.table_keys.numel(), L.ptr(own), L.ptr(corner), L.ptr(weight),
-           L.stream_ptr(dev))
+    L.call("pcs_trilinear_index", pts, off, off.numel() - 1, T, int(sv.grid), *_box(lo, hi), sv.table_keys,
+           sv.table_vals, sv.table_keys.numel(), own, corner, weight, L.stream_ptr(dev))
     return PointVoxelMap(own, corner, weight, sv.num_voxels)
-
-
-def _code(dtype):
-    if dtype == torch.bfloat16:
-        return L.BF16
-    if dtype == torch.float32:
-        return L.F32
-    raise ValueError(f"bf16 or fp32 expected, got {dtype}")
 
 
 def _rows_in(x, name, rows):
@@ -116,7 +107,7 @@ def _rows_in(x, name, rows):
         raise RuntimeError(f"pcs_amd {name} runs on a HIP device only (no CPU fallback)")
     if x.dim() != 2 or x.shape[0] != rows:
         raise ValueError(f"{name}: expected [{rows}, C] features for this map, got {list(x.shape)}")
-    _code(x.dtype)
+    L.dtype_code(x.dtype)
     ck = (x.shape[1] + PV_CH_ALIGN - 1) // PV_CH_ALIGN * PV_CH_ALIGN
     return _pad_channels(x, ck)
 
@@ -126,8 +117,8 @@ def _interp(x, idx, w, M, K, out_dtype):
     if x.shape[0] == 0:   # a level without voxels: nothing to gather
         return torch.zeros(M, x.shape[1], dtype=out_dtype, device=x.device)
     y = torch.empty(M, x.shape[1], dtype=out_dtype, device=x.device)
-    L.call("pcs_rows_interp", L.ptr(x), _code(x.dtype), L.ptr(idx), L.ptr(w), M, K, x.shape[1], L.ptr(y),
-           _code(out_dtype), L.stream_ptr(x.device))
+    L.call("pcs_rows_interp", x, L.dtype_code(x.dtype), idx, w, M, K, x.shape[1], y, L.dtype_code(out_dtype),
+           L.stream_ptr(x.device))
     return y
 
 
@@ -136,8 +127,8 @@ def _segsum(x, src, w, seg_off, scale, M, out_dtype):
     if x.shape[0] == 0:   # no source row: every segment is empty
         return torch.zeros(M, x.shape[1], dtype=out_dtype, device=x.device)
     y = torch.empty(M, x.shape[1], dtype=out_dtype, device=x.device)
-    L.call("pcs_rows_segsum", L.ptr(x), _code(x.dtype), L.ptr(src), L.ptr(w), L.ptr(seg_off), L.ptr(scale), M,
-           x.shape[1], L.ptr(y), _code(out_dtype), L.stream_ptr(x.device))
+    L.call("pcs_rows_segsum", x, L.dtype_code(x.dtype), src, w, seg_off, scale, M, x.shape[1], y,
+           L.dtype_code(out_dtype), L.stream_ptr(x.device))
     return y
 
 
@@ -194,7 +185,7 @@ def voxel_mean(point_feats: torch.Tensor, pvm: PointVoxelMap, out_dtype=torch.bf
     """Per-voxel mean of per-point features: [T, C] (bf16 or fp32) -> [V, C] in out_dtype, fp32 sums
     in point order.  A point whose voxel the level does not hold is ignored (zero gradient); a voxel
     without points is a zero row.  The gradient has point_feats' dtype."""
-    _code(out_dtype)
+    L.dtype_code(out_dtype)
     return _VoxelMeanFn.apply(point_feats, pvm, out_dtype)
 
 
@@ -206,7 +197,7 @@ def devoxelize(voxel_feats: torch.Tensor, pvm: PointVoxelMap, mode: str = "trili
     voxel_feats' dtype."""
     if mode not in ("trilinear", "nearest"):
         raise ValueError(f"devoxelize: mode must be 'trilinear' or 'nearest', got {mode!r}")
-    _code(out_dtype)
+    L.dtype_code(out_dtype)
     return _DevoxelizeFn.apply(voxel_feats, pvm, mode == "trilinear", out_dtype)
 
 

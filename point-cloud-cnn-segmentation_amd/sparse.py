@@ -65,14 +65,13 @@ def _build_pairs(nmap: torch.Tensor):
     nb = L.workspace("pcs_sparse_pairs_workspace", M, taps)
     ws =torch.empty(max(nb // 4, 1), dtype=torch.int32, device=dev)
     counts = torch.empty(taps, dtype=torch.int64, device=dev)
-    L.call("pcs_sparse_pairs_count", L.ptr(nmap), M, taps, L.ptr(ws), L.ptr(counts), st)
+    L.call("pcs_sparse_pairs_count", nmap, M, taps, ws, counts, st)
     tap_off = (ct.c_int64 * (taps + 1))(0, *torch.cumsum(counts, 0).tolist())
     P = int(tap_off[taps])
     pin = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
     pout = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
     ppos = torch.empty(M, taps, dtype=torch.int32, device=dev)
-    L.call("pcs_sparse_pairs_build", L.ptr(nmap), M, taps, L.ptr(ws), L.ptr(counts), L.ptr(pin), L.ptr(pout),
-           L.ptr(ppos), st)
+    L.call("pcs_sparse_pairs_build", nmap, M, taps, ws, counts, pin, pout, ppos, st)
     return pin, pout, ppos, tap_off, P
 
 
@@ -105,8 +104,8 @@ class SparseVoxels:
         """int32 rows of the voxels with these keys (-1: unoccupied), one device lookup each."""
         q = keys.reshape(-1).to(torch.int64).contiguous()
         out = torch.empty(q.numel(), dtype=torch.int32, device=q.device)
-        L.call("pcs_voxel_hash_find", L.ptr(self.table_keys), L.ptr(self.table_vals), self.table_keys.numel(),
-               L.ptr(q), q.numel(), L.ptr(out), L.stream_ptr(q.device))
+        L.call("pcs_voxel_hash_find", self.table_keys, self.table_vals, self.table_keys.numel(), q, q.numel(), out,
+               L.stream_ptr(q.device))
         return out
 
 
@@ -125,9 +124,9 @@ def sparse_from_keys(keys: torch.Tensor, grid: int) -> SparseVoxels:
     tk =torch.empty(cap, dtype=torch.int64, device=dev)
     tv = torch.empty(cap, dtype=torch.int32, device=dev)
     st = L.stream_ptr(dev)
-    L.call("pcs_voxel_hash_build", L.ptr(keys), n, L.ptr(tk), L.ptr(tv), cap, st)
+    L.call("pcs_voxel_hash_build", keys, n, tk, tv, cap, st)
     nbr = torch.empty(n, TAPS, dtype=torch.int32, device=dev)
-    L.call("pcs_sparse_neighbors", L.ptr(tk), L.ptr(tv), cap, L.ptr(keys), n, int(grid), L.ptr(nbr), st)
+    L.call("pcs_sparse_neighbors", tk, tv, cap, keys, n, int(grid), nbr, st)
     return SparseVoxels(keys, tk, tv, nbr, int(grid))
 
 
@@ -138,8 +137,8 @@ def sparse_voxels(rb: RaggedBatch, vb: VoxelBatch, lo=(-1.0, -1.0, -1.0), hi=(1.
     off = rb.offsets.to(dev, torch.int64).contiguous()
     V = vb.batch.points.shape[0]
     keys = torch.empty(V, dtype=torch.int64, device=dev)
-    L.call("pcs_voxel_keys", L.ptr(pts), L.ptr(off), off.numel() - 1, pts.shape[0], int(vb.grid), *_box(lo, hi),
-           L.ptr(vb.voxel_of_point), L.ptr(keys), L.stream_ptr(dev))
+    L.call("pcs_voxel_keys", pts, off, off.numel() - 1, pts.shape[0], int(vb.grid), *_box(lo, hi), vb.voxel_of_point,
+           keys, L.stream_ptr(dev))
     return sparse_from_keys(keys, vb.grid)
 
 
@@ -148,13 +147,12 @@ def _conv_taps(nmap, pairs, x, cin, w, cout, bias, y, ydt, flip=0):
     products, fp32) or, with pairs None, in gathered tiles."""
     (rows, taps), st = nmap.shape, L.stream_ptr(x.device)
     if pairs is None:
-        L.call("pcs_sparse_conv", L.ptr(nmap), rows, taps, L.ptr(x), cin, L.ptr(w), cout, L.ptr(bias), L.ptr(y), ydt,
-               flip, st)
+        L.call("pcs_sparse_conv", nmap, rows, taps, x, cin, w, cout, bias, y, ydt, flip, st)
         return
     pin, _, ppos, tap_off, P = pairs
     z = torch.empty(max(P, 1), cout, dtype=torch.float32, device=x.device)
-    L.call("pcs_sparse_conv_pairs", L.ptr(pin), L.ptr(ppos), ct.addressof(tap_off), taps, rows, L.ptr(x), cin, L.ptr(w),
-           cout, L.ptr(bias), L.ptr(z), L.ptr(y), ydt, flip, st)
+    L.call("pcs_sparse_conv_pairs", pin, ppos, ct.addressof(tap_off), taps, rows, x, cin, w, cout, bias, z, y, ydt,
+           flip, st)
 
 
 def _sparse_wgrad(nmap, pairs_fn, xk, dyb, cin, cout, has_bias, use_pairs):
@@ -164,11 +162,11 @@ def _sparse_wgrad(nmap, pairs_fn, xk, dyb, cin, cout, has_bias, use_pairs):
     if use_pairs:
         pin, pout, _, tap_off, _ = pairs_fn()
         nbytes = L.workspace("pcs_sparse_conv_wgrad_pairs_workspace", ct.addressof(tap_off), taps, rows, cin_k, cout_k)
-        name, head = "pcs_sparse_conv_wgrad_pairs", (L.ptr(pin), L.ptr(pout), ct.addressof(tap_off), taps, rows)
+        name, head = "pcs_sparse_conv_wgrad_pairs", (pin, pout, ct.addressof(tap_off), taps, rows)
     else:
         nbytes = L.workspace("pcs_sparse_conv_wgrad_workspace", rows, taps, cin_k, cout_k)
-        name, head = "pcs_sparse_conv_wgrad", (L.ptr(nmap), rows, taps)
-    head += (L.ptr(xk), cin_k, L.ptr(dyb), cout_k)
+        name, head = "pcs_sparse_conv_wgrad", (nmap, rows, taps)
+    head += (xk, cin_k, dyb, cout_k)
     return _wgrad(name, head, nbytes, taps, cin, cout, cin_k, cout_k, has_bias, xk.device)
 
 
@@ -191,7 +189,7 @@ class _SubMConvFn(torch.autograd.Function):
         y = torch.empty(V, cout_k, dtype=out_dtype, device=x.device)
         pairs = sv.use_pairs()
         _conv_taps(nbr, sv.pairs() if pairs else None, xk, cin_k, wb, cout_k, bk, y,
-                   L.BF16 if out_dtype == torch.bfloat16 else L.F32)
+                   L.dtype_code(out_dtype, what="out_dtype"))
         ctx.save_for_backward(xk, wb, nbr)
         ctx.sv, ctx.pairs = sv, pairs
         ctx.wpairs = PAIR_WGRAD and V > 0 and cin_k * cout_k <= PAIR_WGRAD_MAX_CH2
@@ -246,13 +244,12 @@ def _conv_taps_cat(nmap, pairs, xa, ca, xb, cb, w, cout, bias, y, ydt):
     """_conv_taps on x = [xa | xb] along channels (pcs_sparse_conv_cat, pcs_sparse_conv_cat_pairs)."""
     (rows, taps), st = nmap.shape, L.stream_ptr(xa.device)
     if pairs is None:
-        L.call("pcs_sparse_conv_cat", L.ptr(nmap), rows, taps, L.ptr(xa), ca, L.ptr(xb), cb, L.ptr(w), cout, L.ptr(bias),
-               L.ptr(y), ydt, 0, st)
+        L.call("pcs_sparse_conv_cat", nmap, rows, taps, xa, ca, xb, cb, w, cout, bias, y, ydt, 0, st)
         return
     pin, _, ppos, tap_off, P = pairs
     z = torch.empty(max(P, 1), cout, dtype=torch.float32, device=xa.device)
-    L.call("pcs_sparse_conv_cat_pairs", L.ptr(pin), L.ptr(ppos), ct.addressof(tap_off), taps, rows, L.ptr(xa), ca, L.ptr(xb),
-           cb, L.ptr(w), cout, L.ptr(bias), L.ptr(z), L.ptr(y), ydt, 0, st)
+    L.call("pcs_sparse_conv_cat_pairs", pin, ppos, ct.addressof(tap_off), taps, rows, xa, ca, xb, cb, w, cout, bias, z,
+           y, ydt, 0, st)
 
 
 def _dgrad_taps_cat(nmap, pairs, dyb, cout, wt, dxa, ca, dxb, cb):
@@ -260,13 +257,12 @@ def _dgrad_taps_cat(nmap, pairs, dyb, cout, wt, dxa, ca, dxb, cb):
     (pcs_sparse_conv_cat_dgrad, pcs_sparse_conv_cat_dgrad_pairs); wt = _weight_t(wb)."""
     (rows, taps), st = nmap.shape, L.stream_ptr(dyb.device)
     if pairs is None:
-        L.call("pcs_sparse_conv_cat_dgrad", L.ptr(nmap), rows, taps, L.ptr(dyb), cout, L.ptr(wt), L.ptr(dxa), ca,
-               L.ptr(dxb), cb, L.BF16, 1, st)
+        L.call("pcs_sparse_conv_cat_dgrad", nmap, rows, taps, dyb, cout, wt, dxa, ca, dxb, cb, L.BF16, 1, st)
         return
     pin, _, ppos, tap_off, P = pairs
     z = torch.empty(max(P, 1), ca + cb, dtype=torch.float32, device=dyb.device)
-    L.call("pcs_sparse_conv_cat_dgrad_pairs", L.ptr(pin), L.ptr(ppos), ct.addressof(tap_off), taps, rows, L.ptr(dyb), cout,
-           L.ptr(wt), L.ptr(z), L.ptr(dxa), ca, L.ptr(dxb), cb, L.BF16, 1, st)
+    L.call("pcs_sparse_conv_cat_dgrad_pairs", pin, ppos, ct.addressof(tap_off), taps, rows, dyb, cout, wt, z, dxa, ca,
+           dxb, cb, L.BF16, 1, st)
 
 
 def _sparse_wgrad_cat(nmap, pairs_fn, xa, xb, dyb, has_bias, use_pairs):
@@ -277,11 +273,11 @@ def _sparse_wgrad_cat(nmap, pairs_fn, xa, xb, dyb, has_bias, use_pairs):
     if use_pairs:
         pin, pout, _, tap_off, _ = pairs_fn()
         nbytes = L.workspace("pcs_sparse_conv_wgrad_pairs_workspace", ct.addressof(tap_off), taps, rows, cin, cout)
-        name, head = "pcs_sparse_conv_cat_wgrad_pairs", (L.ptr(pin), L.ptr(pout), ct.addressof(tap_off), taps, rows)
+        name, head = "pcs_sparse_conv_cat_wgrad_pairs", (pin, pout, ct.addressof(tap_off), taps, rows)
     else:
         nbytes = L.workspace("pcs_sparse_conv_wgrad_workspace", rows, taps, cin, cout)
-        name, head = "pcs_sparse_conv_cat_wgrad", (L.ptr(nmap), rows, taps)
-    head += (L.ptr(xa), ca, L.ptr(xb), cb, L.ptr(dyb), cout)
+        name, head = "pcs_sparse_conv_cat_wgrad", (nmap, rows, taps)
+    head += (xa, ca, xb, cb, dyb, cout)
     return _wgrad(name, head, nbytes, taps, cin, cout, cin, cout, has_bias, xa.device)
 
 
@@ -301,7 +297,7 @@ class _SubMConvCatFn(torch.autograd.Function):
         pairs = sv.use_pairs()
         if V > 0:
             _conv_taps_cat(nbr, sv.pairs() if pairs else None, xa, ca, xb, cb, wb, cout, bk, y,
-                           L.BF16 if out_dtype == torch.bfloat16 else L.F32)
+                           L.dtype_code(out_dtype, what="out_dtype"))
         ctx.save_for_backward(xa, xb, wb, nbr)
         ctx.sv, ctx.pairs = sv, pairs
         ctx.wpairs = PAIR_WGRAD and V > 0 and (ca + cb) * cout <= PAIR_WGRAD_MAX_CH2
@@ -431,7 +427,7 @@ def coarsen(sv: SparseVoxels):
     st = L.stream_ptr(dev)
     pkey = torch.empty(V, dtype=torch.int64, device=dev)
     tap = torch.empty(V, dtype=torch.int32, device=dev)
-    L.call("pcs_sparse_coarse_keys", L.ptr(sv.keys), V, sv.grid, L.ptr(pkey), L.ptr(tap), st)
+    L.call("pcs_sparse_coarse_keys", sv.keys, V, sv.grid, pkey, tap, st)
     ckeys, crow = torch.unique(pkey, sorted=True, return_inverse=True)
     svc = sparse_from_keys(ckeys, sv.grid // 2)
     Vc = svc.num_voxels
@@ -439,7 +435,7 @@ def coarsen(sv: SparseVoxels):
     parent = torch.empty(V, dtype=torch.int32, device=dev)
     up = torch.empty(V, K2_TAPS, dtype=torch.int32, device=dev)
     crow = crow.to(torch.int64).contiguous()
-    L.call("pcs_sparse_coarse_maps", L.ptr(crow), L.ptr(tap), V, Vc, L.ptr(child), L.ptr(parent), L.ptr(up), st)
+    L.call("pcs_sparse_coarse_maps", crow, tap, V, Vc, child, parent, up, st)
     return svc, CoarseLink(child, parent, tap, up, V, Vc)
 
 
@@ -447,8 +443,8 @@ def _conv_rows(link, x, cin, w, cout, bias, y, ydt):
     """y[f] = b + W[tap[f]] x[parent[f]]: one tap per output row (pcs_sparse_conv_rows)."""
     pin, pout, _, tap_off, P = link.up_pairs()
     assert P == link.fine, "the up map has one pair per fine voxel"
-    L.call("pcs_sparse_conv_rows", L.ptr(pin), L.ptr(pout), ct.addressof(tap_off), K2_TAPS, link.fine, L.ptr(x), cin,
-           L.ptr(w), cout, L.ptr(bias), L.ptr(y), ydt, L.stream_ptr(x.device))
+    L.call("pcs_sparse_conv_rows", pin, pout, ct.addressof(tap_off), K2_TAPS, link.fine, x, cin, w, cout, bias, y, ydt,
+           L.stream_ptr(x.device))
 
 
 def _conv_cells(link, x, cin, w, cout, bias, y, ydt):
@@ -475,7 +471,7 @@ class _StrideConvFn(torch.autograd.Function):
             raise ValueError(f"weight has {wk.shape[1] // K2_TAPS} input channels, x has {cin}")
         xk, wb, bk, cin_k, cout_k = _conv_operands(x, wk, bias, K2_TAPS, CH_ALIGN)
         y = torch.empty(rows_out, cout_k, dtype=out_dtype, device=x.device)
-        ydt = L.BF16 if out_dtype == torch.bfloat16 else L.F32
+        ydt = L.dtype_code(out_dtype, what="out_dtype")
         (_conv_rows if up else _conv_cells)(link, xk, cin_k, wb, cout_k, bk, y, ydt)
         ctx.save_for_backward(xk, wb)
         ctx.link, ctx.up = link, up

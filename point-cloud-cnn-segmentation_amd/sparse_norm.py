@@ -25,14 +25,6 @@ from .sparse import SparseVoxels, SubMConv3d
 MAX_CHANNELS = 1024
 
 
-def _code(dtype, what):
-    if dtype == torch.bfloat16:
-        return L.BF16
-    if dtype == torch.float32:
-        return L.F32
-    raise ValueError(f"sparse_batch_norm: {what} must be bf16 or fp32, got {dtype}")
-
-
 def _check_channels(c, x_dtype, out_dtype):
     e = 8 if torch.bfloat16 in (x_dtype, out_dtype) else 4
     if c < e or c % e or c > MAX_CHANNELS:
@@ -63,7 +55,8 @@ class _SparseBNFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, running_mean, running_var, residual, training, momentum, eps, relu, out_dtype):
         V, C = x.shape
         dev, st = x.device, L.stream_ptr(x.device)
-        xdt, ydt = _code(x.dtype, "x"), _code(out_dtype, "out_dtype")
+        xdt = L.dtype_code(x.dtype, what="sparse_batch_norm: x")
+        ydt = L.dtype_code(out_dtype, what="sparse_batch_norm: out_dtype")
         x = x.contiguous()
         res = residual.contiguous() if residual is not None else None
         gamma, beta = weight.detach().float().contiguous(), bias.detach().float().contiguous()
@@ -73,18 +66,15 @@ class _SparseBNFn(torch.autograd.Function):
         nb, rpb = _geometry(V, C)
         if training:
             stats = torch.empty(nb, C, 2, dtype=torch.float32, device=dev)
-            L.call("pcs_sparse_bn_stats", L.ptr(x), xdt, V, C, nb, rpb, L.ptr(stats), st)
-            L.call("pcs_bn_fwd_finalize", L.ptr(stats), 1, V, C, nb, rpb, L.ptr(gamma), L.ptr(beta), None,
-                   L.ptr(running_mean), L.ptr(running_var), float(momentum), float(eps), 1, L.ptr(mean), L.ptr(rstd),
-                   L.ptr(scale), L.ptr(shift), None, st)
+            L.call("pcs_sparse_bn_stats", x, xdt, V, C, nb, rpb, stats, st)
+            L.call("pcs_bn_fwd_finalize", stats, 1, V, C, nb, rpb, gamma, beta, None, running_mean, running_var,
+                   float(momentum), float(eps), 1, mean, rstd, scale, shift, None, st)
         else:
-            L.call("pcs_bn_eval_coefs", L.ptr(gamma), L.ptr(beta), L.ptr(running_mean), L.ptr(running_var), None,
-                   float(eps), C, L.ptr(scale), L.ptr(shift), st)
+            L.call("pcs_bn_eval_coefs", gamma, beta, running_mean, running_var, None, float(eps), C, scale, shift, st)
             if any(ctx.needs_input_grad):   # the backward's xhat is (x - running_mean) * rstd_running
                 mean.copy_(running_mean)
                 rstd.copy_(torch.rsqrt(running_var.double() + eps))
-        L.call("pcs_sparse_bn_apply", L.ptr(x), xdt, L.ptr(res), L.ptr(scale), L.ptr(shift), int(relu), V, C, L.ptr(y),
-               ydt, st)
+        L.call("pcs_sparse_bn_apply", x, xdt, res, scale, shift, int(relu), V, C, y, ydt, st)
         ctx.save_for_backward(x, y if relu else None, mean, rstd, gamma)
         ctx.cfg = (training, relu, xdt, ydt, nb, rpb, weight.dtype, bias.dtype)
         return y
@@ -98,7 +88,7 @@ class _SparseBNFn(torch.autograd.Function):
         V, C = x.shape
         dev, st = x.device, L.stream_ptr(x.device)
         dy = dy.contiguous()
-        if _code(dy.dtype, "the output gradient") != ydt:
+        if L.dtype_code(dy.dtype, what="sparse_batch_norm: the output gradient") != ydt:
             raise ValueError("sparse_batch_norm backward: the output gradient must have the output's dtype")
         dx = dw = db = None
         dz = torch.empty_like(dy) if relu else dy          # without a gate dz is dy itself
@@ -109,19 +99,18 @@ class _SparseBNFn(torch.autograd.Function):
                     None)
         if relu or need_x or need_w or need_b:
             stats = torch.empty(nb, C, 2, dtype=torch.float32, device=dev)
-            L.call("pcs_sparse_bn_bwd_reduce", L.ptr(dy), L.ptr(y), ydt, L.ptr(x), xdt, L.ptr(mean), L.ptr(rstd),
-                   int(relu), V, C, nb, rpb, L.ptr(dz) if relu else None, L.ptr(stats), st)
+            L.call("pcs_sparse_bn_bwd_reduce", dy, y, ydt, x, xdt, mean, rstd, int(relu), V, C, nb, rpb,
+                   dz if relu else None, stats, st)
         if need_x or need_w or need_b:
             out = torch.empty(5, C, dtype=torch.float32, device=dev)
             alpha, beta_c, gamma_c, dgamma, dbeta = out[0], out[1], out[2], out[3], out[4]
-            L.call("pcs_bn_bwd_finalize", L.ptr(stats), 1, V, C, nb, L.ptr(mean), L.ptr(rstd), L.ptr(gamma), None,
-                   L.ptr(alpha), L.ptr(beta_c), L.ptr(gamma_c), L.ptr(dgamma), L.ptr(dbeta), None, None, st)
+            L.call("pcs_bn_bwd_finalize", stats, 1, V, C, nb, mean, rstd, gamma, None, alpha, beta_c, gamma_c, dgamma,
+                   dbeta, None, None, st)
             if need_x:
                 if not training:   # the statistics are constants: dx = scale * dz
                     out[1:3].zero_()
                 dx = torch.empty_like(x)
-                L.call("pcs_sparse_bn_bwd_apply", L.ptr(dz), ydt, L.ptr(x), xdt, L.ptr(alpha), L.ptr(beta_c),
-                       L.ptr(gamma_c), V, C, L.ptr(dx), st)
+                L.call("pcs_sparse_bn_bwd_apply", dz, ydt, x, xdt, alpha, beta_c, gamma_c, V, C, dx, st)
             dw = dgamma.to(wdtype) if need_w else None
             db = dbeta.to(bdtype) if need_b else None
         return dx, dw, db, None, None, dz if need_r else None, None, None, None, None, None
@@ -139,7 +128,8 @@ def sparse_batch_norm(x, weight, bias, running_mean, running_var, training, mome
     if x.dim() != 2:
         raise ValueError(f"sparse_batch_norm: x must be [V, C], got {list(x.shape)}")
     out_dtype = x.dtype if out_dtype is None else out_dtype
-    _code(x.dtype, "x"), _code(out_dtype, "out_dtype")
+    L.dtype_code(x.dtype, what="sparse_batch_norm: x")
+    L.dtype_code(out_dtype, what="sparse_batch_norm: out_dtype")
     V, C = x.shape
     _check_channels(C, x.dtype, out_dtype)
     if momentum is None:

@@ -104,8 +104,8 @@ class FusedTrainStep:
         if labels.dtype != torch.int64:
             labels = labels.long()
         s = L.stream_ptr()
-        L.call("pcs_ce_weight_sum", L.ptr(labels), labels.numel(), L.ptr(self.class_weight),
-               model.num_classes, L.ptr(self.counts), L.ptr(self.wsum), s)
+        L.call("pcs_ce_weight_sum", labels, labels.numel(), self.class_weight, model.num_classes, self.counts,
+               self.wsum, s)
         ddp = self._distributed()
         if seed is None:
             seed = model._next_seed()
@@ -117,7 +117,7 @@ class FusedTrainStep:
         for bn, _ in BNS:
             getattr(model, bn).num_batches_tracked.add_(1)
         hb = sv.head
-        L.call("pcs_reduce_partials", L.ptr(hb["loss_partial"]), hb["nch"], 1, 1.0, L.ptr(ext), 1, 1, s)
+        L.call("pcs_reduce_partials", hb["loss_partial"], hb["nch"], 1, 1.0, ext, 1, 1, s)
         if ddp:
             ext[1:3].copy_(self.wsum[:2])
             buckets = GradientBuckets(gflat, eng.buckets, self.pg)

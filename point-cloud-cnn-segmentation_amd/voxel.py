@@ -15,7 +15,6 @@ semantics are build-defined ("not reference parity").
 """
 from __future__ import annotations
 
-import ctypes as ct
 from dataclasses import dataclass
 
 import torch
@@ -46,7 +45,7 @@ def voxel_ids(points: torch.Tensor, grid: int, lo=(-1.0, -1.0, -1.0), hi=(1.0, 1
         raise RuntimeError("voxel_ids runs on a HIP device only (no CPU fallback)")
     pts = points.contiguous().float()
     out = torch.empty(pts.shape[0], dtype=torch.int64, device=pts.device)
-    L.call("pcs_voxel_ids", L.ptr(pts), pts.shape[0], int(grid), *_box(lo, hi), L.ptr(out), L.stream_ptr())
+    L.call("pcs_voxel_ids", pts, pts.shape[0], int(grid), *_box(lo, hi), out, L.stream_ptr())
     return out
 
 
@@ -70,9 +69,8 @@ def voxelize(rb: RaggedBatch, grid: int, lo=(-1.0, -1.0, -1.0), hi=(1.0, 1.0, 1.
     vcnt = torch.empty(T, dtype=torch.int64, device=device)
     voff = torch.empty(B + 1, dtype=torch.int64, device=device)
     nv = torch.empty(1, dtype=torch.int64, device=device)
-    L.call("pcs_voxelize", L.ptr(pts), L.ptr(lab), L.ptr(off), B, T, int(grid), *_box(lo, hi), int(num_classes),
-           L.ptr(ws), ws.numel(), L.ptr(vop), L.ptr(vpts), L.ptr(vlab), L.ptr(vcnt), L.ptr(voff), L.ptr(nv),
-           L.stream_ptr(device))
+    L.call("pcs_voxelize", pts, lab, off, B, T, int(grid), *_box(lo, hi), int(num_classes), ws, ws.numel(), vop, vpts,
+           vlab, vcnt, voff, nv, L.stream_ptr(device))
     V = int(nv.item())
     return VoxelBatch(RaggedBatch(vpts[:V], vlab[:V], voff), vcnt[:V], vop, int(grid))
 
@@ -87,13 +85,12 @@ def to_points(voxel_logits: torch.Tensor, vb: VoxelBatch) -> torch.Tensor:
     if x.dim() == 3:
         B, Nv = x.shape[0], x.shape[1]
         idx = torch.empty(T, dtype=torch.int64, device=out_dev)
-        L.call("pcs_voxel_padded_index", L.ptr(vb.voxel_of_point), T, L.ptr(vb.batch.offsets), B, Nv, L.ptr(idx),
-               L.stream_ptr(out_dev))
+        L.call("pcs_voxel_padded_index", vb.voxel_of_point, T, vb.batch.offsets, B, Nv, idx, L.stream_ptr(out_dev))
         src = x.view(B * Nv, C)
     else:
         idx, src = vb.voxel_of_point, x
     out = torch.empty(T, C, dtype=torch.float32, device=out_dev)
-    L.call("pcs_gather_rows", L.ptr(src), src.stride(0), L.ptr(idx), T, C, L.ptr(out), L.stream_ptr(out_dev))
+    L.call("pcs_gather_rows", src, src.stride(0), idx, T, C, out, L.stream_ptr(out_dev))
     return out
 
 
@@ -131,7 +128,7 @@ def _bf16_2d(t, rows, cols):
     if t.dtype == torch.bfloat16:
         return t
     out = torch.empty(rows, cols, dtype=torch.bfloat16, device=t.device)
-    L.call("pcs_cast_weight", L.ptr(t.float()), rows, cols, cols, L.BF16, L.ptr(out), None, L.stream_ptr(t.device))
+    L.call("pcs_cast_weight", t.float(), rows, cols, cols, L.BF16, out, None, L.stream_ptr(t.device))
     return out
 
 
@@ -172,7 +169,7 @@ def _weight_t(wb, taps):
     """wb [Cout, taps * Cin] transposed per tap (pcs_conv3d_weight_t): an input gradient's weight."""
     cout_k, cin_k = wb.shape[0], wb.shape[1] // taps
     wt = torch.empty(cin_k, taps * cout_k, dtype=torch.bfloat16, device=wb.device)
-    L.call("pcs_conv3d_weight_t", L.ptr(wb), cout_k, taps, cin_k, L.ptr(wt), L.stream_ptr(wb.device))
+    L.call("pcs_conv3d_weight_t", wb, cout_k, taps, cin_k, wt, L.stream_ptr(wb.device))
     return wt
 
 
@@ -182,7 +179,7 @@ def _wgrad(name, head, nbytes, taps, cin, cout, cin_k, cout_k, has_bias, dev):
     ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
     dwk = torch.empty(cout_k, taps * cin_k, dtype=torch.float32, device=dev)
     db = torch.empty(cout_k, dtype=torch.float32, device=dev) if has_bias else None
-    L.call(name, *head, L.ptr(ws), nbytes, L.ptr(dwk), L.ptr(db), L.stream_ptr(dev))
+    L.call(name, *head, ws, nbytes, dwk, db, L.stream_ptr(dev))
     if (cin_k, cout_k) != (cin, cout):
         dwk = dwk.reshape(cout_k, taps, cin_k)[:cout, :, :cin].reshape(cout, taps * cin)
         db = db[:cout] if has_bias else None
@@ -207,8 +204,7 @@ class _Conv3dFn(torch.autograd.Function):
         xk, wb, bk, cin_k, cout_k = _conv_operands(x, wk, bias, taps, DENSE_CH_ALIGN)
         g = _geom(B, (D, H, W), cin_k, cout_k, k, s, p, transposed, op)
         y = torch.empty(B, g.Do, g.Ho, g.Wo, cout_k, dtype=out_dtype, device=x.device)
-        L.call("pcs_conv3d", ct.byref(g), L.ptr(xk), L.ptr(wb), L.ptr(bk), L.ptr(y),
-               L.BF16 if out_dtype == torch.bfloat16 else L.F32, L.stream_ptr(x.device))
+        L.call("pcs_conv3d", g, xk, wb, bk, y, L.dtype_code(out_dtype, what="out_dtype"), L.stream_ptr(x.device))
         ctx.save_for_backward(xk, wb)
         ctx.cfg = (k, s, p, transposed, bias is not None, op, cin, cout)
         return y if cout_k == cout else y[..., :cout].contiguous()
@@ -238,13 +234,12 @@ class _Conv3dFn(torch.autograd.Function):
             if (gb.Do, gb.Ho, gb.Wo) != (D, H, W):
                 raise ValueError("input gradient: the strided output grid does not map back onto the input grid")
             dx = torch.empty_like(xk)
-            L.call("pcs_conv3d", ct.byref(gb), L.ptr(dyb), L.ptr(wt), None, L.ptr(dx), L.BF16, st)
+            L.call("pcs_conv3d", gb, dyb, wt, None, dx, L.BF16, st)
             if cin_k != cin:
                 dx = dx[..., :cin].contiguous()
         if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            nbytes = L.workspace("pcs_conv3d_wgrad_workspace", ct.byref(g))
-            dwk, db = _wgrad("pcs_conv3d_wgrad", (ct.byref(g), L.ptr(xk), L.ptr(dyb)), nbytes, taps, cin, cout, cin_k,
-                             cout_k, has_bias, dev)
+            nbytes = L.workspace("pcs_conv3d_wgrad_workspace", g)
+            dwk, db = _wgrad("pcs_conv3d_wgrad", (g, xk, dyb), nbytes, taps, cin, cout, cin_k, cout_k, has_bias, dev)
         return dx, dwk, db, None, None, None, None, None, None
 
 

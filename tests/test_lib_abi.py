@@ -1,13 +1,17 @@
 """CPU-side checks of the C ABI: the library loads and exports every declared symbol."""
 import ctypes as ct
+import json
 import os
 import re
+import shutil
+import subprocess
 
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(REPO, "include", "pcs.h")
 LIB = os.path.join(REPO, "point-cloud-cnn-segmentation_amd", "csrc", "libpcs.so")
+SNAPSHOT = os.path.join(REPO, "tests", "golden", "abi_tables.json")
 
 
 def declared_functions():
@@ -37,11 +41,91 @@ def test_library_exports_every_declared_symbol():
     assert L.ABI_VERSION == want
 
 
-@pytest.mark.skipif(not os.path.exists(LIB), reason="libpcs.so not built")
-def test_binding_signatures_cover_header():
+def _type_name(t):
+    if isinstance(t, type) and issubclass(t, ct._Pointer):
+        return f"POINTER({t._type_.__name__})"
+    return t.__name__
+
+
+def abi_tables(L):
+    """What a binding module says about the ABI, as plain data: per function the ctypes names of the
+    result and of every argument, per struct class its (field, ctypes name) list in order."""
+    structs = [c for c in vars(L).values()
+               if isinstance(c, type) and issubclass(c, ct.Structure) and c is not ct.Structure]
+    return {"abi_version": L.ABI_VERSION,
+            "functions": {n: [_type_name(res), [_type_name(a) for a in args]] for n, res, args in L.SIGNATURES},
+            "structs": {c.__name__: [[f, _type_name(t)] for f, t in c._fields_] for c in structs}}
+
+
+def test_derived_tables_equal_the_recorded_snapshot():
+    """The tables _lib.py derives from include/pcs.h against tests/golden/abi_tables.json, recorded
+    from the hand-written tables they replaced: an ABI change is a reviewable data diff."""
     import pcs_amd._lib as L
-    bound = {n for n, _, _ in L.SIGNATURES}
-    assert set(declared_functions()) == bound
+    got, want = abi_tables(L), json.load(open(SNAPSHOT))
+    assert len(L.SIGNATURES) == len(got["functions"]) and set(got["functions"]) == set(declared_functions())
+    diff = [f"{kind}.{k}" for kind in ("functions", "structs")
+            for k in sorted(set(got[kind]) | set(want[kind])) if got[kind].get(k) != want[kind].get(k)]
+    assert not diff and got == want, (
+        f"include/pcs.h no longer gives the recorded ABI tables: {diff or 'abi_version'}.  After adding an entry "
+        "point, regenerate the snapshot (`python tests/test_lib_abi.py`) and review its diff; if a struct or an "
+        "existing signature changed, bump PCS_ABI_VERSION in include/pcs.h as well.")
+
+
+def test_struct_layouts_agree_with_a_c_compiler(tmp_path):
+    """sizeof and every offsetof of the six argument structs, from a C99 program that includes pcs.h."""
+    cc = shutil.which("cc")
+    if cc is None:
+        pytest.skip("no C compiler (cc) on PATH")
+    import pcs_amd._lib as L
+    hdr = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    c_names = re.findall(r"typedef\s+struct\s*\{[^{}]*\}\s*(\w+)\s*;", hdr)
+    classes = {c: getattr(L, "".join(p.capitalize() for p in c.split("_")[1:])) for c in c_names}
+    assert len(classes) == 6
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "pcs.h"', 'int main(void) {']
+    for c, cls in classes.items():
+        lines.append(f'  printf("{c} %zu\\n", sizeof({c}));')
+        lines += [f'  printf("{c}.{f} %zu\\n", offsetof({c}, {f}));' for f, _ in cls._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["  return 0;", "}"]) + "\n")
+    exe = tmp_path / "layout"
+    subprocess.run([cc, "-std=c99", "-I", os.path.dirname(HEADER), "-o", str(exe), str(src)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    got = dict(ln.split() for ln in out.splitlines())
+    want = {}
+    for c, cls in classes.items():
+        want[c] = str(ct.sizeof(cls))
+        want.update({f"{c}.{f}": str(getattr(cls, f).offset) for f, _ in cls._fields_})
+    assert got == want
+    assert [want[c] for c in c_names] == ["288", "184", "208", "184", "128", "56"]
+
+
+@pytest.mark.parametrize("text,names", [
+    ("typedef struct ihipStream_t *pcs_stream_t;\nint pcs_f(const double *x, pcs_stream_t stream);", "const double *x"),
+    ("int pcs_f(int32_t n);\ntypedef struct { int32_t a; float b;\nint pcs_g(void);", "typedef struct { int32_t a;"),
+    ("enum { PCS_A = 1, PCS_B };", "PCS_B"),
+    ("int pcs_f(unsigned n);", "unsigned n"),
+    ("typedef struct { int32_t a; uint8_t b; } pcs_t;", "uint8_t b"),
+    ("#pragma pack(1)\nint pcs_f(void);", "#pragma pack(1)"),
+])
+def test_parser_refuses_what_it_does_not_know(text, names):
+    """An unknown parameter type, an unterminated struct, an enumerator without a value (and an
+    unknown scalar, a by-value field of a pointee-only type, an unknown directive): each raises and
+    names the offending text; nothing is guessed."""
+    import pcs_amd._lib as L
+    with pytest.raises(ImportError, match=re.escape(names)):
+        L.parse_header(text)
+
+
+def test_parser_reads_multi_declarator_lines():
+    import pcs_amd._lib as L
+    consts, structs, functions = L.parse_header(
+        "#define PCS_ABI_VERSION 7\nenum { PCS_X = -3, };\n"
+        "typedef struct { const void *A, *A2; const uint8_t *m; float k; int64_t n, ld; } pcs_t;\n"
+        "int64_t pcs_q(pcs_t *args);")
+    assert consts == {"ABI_VERSION": 7, "X": -3}
+    assert structs == {"pcs_t": [("A", ct.c_void_p), ("A2", ct.c_void_p), ("m", ct.c_void_p), ("k", ct.c_float),
+                                 ("n", ct.c_int64), ("ld", ct.c_int64)]}
+    assert functions == [("pcs_q", "int64_t", [("args", "pcs_t", True, False)])]
 
 
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libpcs.so not built")
@@ -199,3 +283,19 @@ def test_sparse_pairs_argument_validation_without_gpu():
                                      None) == -1000
     assert lib.pcs_sparse_conv_pairs(1, 1, ta, 27, 100, 1, 64, 1, 48, None, 1, 1, L.BF16, 0, None) == -1000   # Cout
     assert lib.pcs_sparse_conv_pairs(1, 1, ta, 27, 100, 1, 64, 1, 64, None, None, 1, L.BF16, 0, None) == -1000   # no Z
+
+
+def write_snapshot(tables):
+    """One line per function and per struct, sorted: a new entry point is one added line."""
+    def rows(d):
+        return ",\n".join(f"  {json.dumps(k)}: {json.dumps(v)}" for k, v in sorted(d.items()))
+    with open(SNAPSHOT, "w") as f:
+        f.write(f'{{\n "abi_version": {tables["abi_version"]},\n "functions": {{\n{rows(tables["functions"])}\n }},\n'
+                f' "structs": {{\n{rows(tables["structs"])}\n }}\n}}\n')
+
+
+if __name__ == "__main__":   # regenerate the snapshot from include/pcs.h as _lib.py reads it
+    import sys
+    sys.path.insert(0, REPO)
+    import pcs_amd._lib as L
+    write_snapshot(abi_tables(L))

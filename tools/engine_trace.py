@@ -6,8 +6,9 @@
 
 The counterpart of tools/asm_equal.py for a refactor of the orchestration (engine.py) that must
 not change what runs.  PKGDIR is a copy of point-cloud-cnn-segmentation_amd/ as it was at the
-revision to compare with (`git archive REV point-cloud-cnn-segmentation_amd | tar -x -C DIR`); its
-csrc/ is not used: both sides load the in-tree libpcs.so (PCS_LIB).  Each side runs every scenario
+revision to compare with (`git archive REV point-cloud-cnn-segmentation_amd include | tar -x -C DIR`:
+a binding that reads include/pcs.h looks for it beside its package); its csrc/ is not used: both sides
+load the in-tree libpcs.so (PCS_LIB).  Each side runs every scenario
 in a fresh child process.  A scenario's trace is one line per call on the loaded library, through
 _lib.call, _lib.workspace or directly: the function, every scalar argument and scalar struct field,
 NULL / ptr for every pointer, main / side for the stream, a size query's return value, and
