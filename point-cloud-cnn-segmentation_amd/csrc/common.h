@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/pcs.h"
+#include "route.h"
 
 #define PCS_DEV __device__ __forceinline__
 #define PCS_DEV_FWD __device__ __forceinline__
@@ -175,74 +176,25 @@ PCS_DEV bool pool_min_step(float v, float cur, int ci) {
   return (v < cur) | ((v != v) & (cur == cur)) | (ci == PCS_POOL_NONE);
 }
 
-// row-tile geometry of one scene-aware chunk (rows never straddle scenes)
-struct ChunkGeo {
-  int64_t scene_rows;   // N: rows per scene (padded cloud length)
-  int tiles_per_scene;  // ceil(N / BM)
-  int tiles_per_chunk;
-  int chunks_per_scene;
-};
-
 __host__ __device__ inline int64_t pcs_min64(int64_t a, int64_t b) { return a < b ? a : b; }
 __host__ __device__ inline int64_t pcs_max64(int64_t a, int64_t b) { return a > b ? a : b; }
 
-// Scene-aligned chunk geometry: fills a->chunks_per_scene (auto when <= 0, aiming at
-// ~target workgroups over ncb column blocks) and returns rows per chunk.
-inline int64_t pcs_fill_geometry(pcs_gemm_args *a, int64_t tile, int64_t target, int64_t ncb) {
-  const int64_t tps = (a->scene_rows + tile - 1) / tile;
-  int64_t cps = a->chunks_per_scene;
-  if (cps <= 0) cps = (target + a->num_scenes * ncb - 1) / (a->num_scenes * ncb);
-  if (cps > tps) cps = tps;
-  if (cps < 1) cps = 1;
-  const int64_t tpc = (tps + cps - 1) / cps;
-  cps = (tps + tpc - 1) / tpc;  // no empty chunks
-  a->chunks_per_scene = (int32_t)cps;
-  return tpc * tile;
-}
-
-// wide-layer bf16 kernel (gemm_big.hip)
-bool pcs_gemm_big_applicable(const pcs_gemm_args &a);
-int pcs_gemm_big_launch(const pcs_gemm_args &a, int tiles_per_scene, int tiles_per_chunk,
-                        hipStream_t s);
-constexpr int PCS_BIG_BM = 256;
-// LDS-DMA 256x256 kernel for the RAW-operand global_feat GEMMs (gemm_glds.hip)
-bool pcs_gemm_glds_applicable(const pcs_gemm_args &a);
-// gemm_wres.hip: W-resident LDS-DMA stream for conv5's BN+ReLU pass with an fp8 store (K = 128)
-bool pcs_gemm_wres_applicable(const pcs_gemm_args &a);
+// One launcher per kernel family: dispatch.hip picks the family (route.h), the launcher its
+// template instantiation.
+int pcs_gemm_nt_launch(const pcs_gemm_args &a, int tiles_per_scene, int tiles_per_chunk, hipStream_t s);
+int pcs_gemm_big_launch(const pcs_gemm_args &a, int tiles_per_scene, int tiles_per_chunk, hipStream_t s);
+int pcs_gemm_glds_launch(const pcs_gemm_args &a, int tiles_per_scene, int tiles_per_chunk, hipStream_t s);
 int pcs_gemm_wres_launch(const pcs_gemm_args &g, int64_t rows_per_chunk, hipStream_t s);
-int pcs_gemm_glds_launch(const pcs_gemm_args &a, int tiles_per_scene, int tiles_per_chunk,
-                         hipStream_t s);
-// fused seg_conv2 / seg_conv3 input + weight gradient (fused_seg4.hip)
-bool pcs_seg4_applicable(const pcs_gemm_args &a);
-int64_t pcs_seg4_geometry(pcs_gemm_args *a);
-int pcs_seg4_launch(const pcs_gemm_args &a, float *wpart, hipStream_t s);
-// conv5's folded input gradient as one LDS-DMA stream (fused_c5.hip)
-bool pcs_c5_dgrad_class(const pcs_gemm_args &a);
-bool pcs_c5_dgrad_applicable(const pcs_gemm_args &a);
 int pcs_c5_dgrad_launch(const pcs_gemm_args &a, int64_t rows_per_chunk, hipStream_t s);
-// streaming forward of the narrow-K BN+ReLU layers (fwd_stream.hip): output columns per
-// workgroup (0 = not this kernel's class; shapes only, the chunk geometry), applicability, launch
-int pcs_fwd_stream_nb(const pcs_gemm_args &a, int *target_workgroups);
-bool pcs_fwd_stream_applicable(const pcs_gemm_args &a);
 int pcs_fwd_stream_launch(const pcs_gemm_args &a, int64_t rows_per_chunk, hipStream_t s);
-// the streamed CE head (head_stream.hip; pcs_head): class (shapes / modes), grid target, launch
-bool pcs_head_stream_class(const pcs_head_args &a);
-int pcs_head_stream_target();
+int pcs_seg4_launch(const pcs_gemm_args &a, float *wpart, int64_t rows_per_chunk, hipStream_t s);
+int pcs_dgrad_wgrad_bn_launch(const pcs_gemm_args &a, float *wpart, int64_t rows_per_chunk, hipStream_t s);
 int pcs_head_stream_launch(const pcs_head_args &a, int64_t rows_per_chunk, hipStream_t s);
-// the Gram of relu(bn(Y)) at C = 128 in one pass over Y (wgrad_c5.hip; pcs_gram)
-bool pcs_gram128_class(const pcs_wgrad_args &a);
-bool pcs_gram128_applicable(const pcs_wgrad_args &a);
-int pcs_gram128_splits(const pcs_wgrad_args &a);
-int pcs_gram128_launch(const pcs_wgrad_args &a, hipStream_t s);
-// conv5's R = dz5^T relu(bn4(y4)) as an LDS-DMA stream (wgrad_c5.hip)
-bool pcs_wgrad_c5_class(const pcs_wgrad_args &a);
-bool pcs_wgrad_c5_applicable(const pcs_wgrad_args &a);
-int pcs_wgrad_c5_splits(const pcs_wgrad_args &a);
-int pcs_wgrad_c5_launch(const pcs_wgrad_args &a, int64_t rows_per_split, hipStream_t s);
-// wide-layer bf16 weight-gradient kernel (gemm_big_tn.hip)
-bool pcs_wgrad_big_applicable(const pcs_wgrad_args &a);
-int pcs_wgrad_big_splits(const pcs_wgrad_args &a);
+int pcs_wgrad_tn_launch(const pcs_wgrad_args &a, int64_t rows_per_split, hipStream_t s);
 int pcs_wgrad_big_launch(const pcs_wgrad_args &a, hipStream_t s);
+int pcs_wgrad_c5_launch(const pcs_wgrad_args &a, int64_t rows_per_split, hipStream_t s);
+int pcs_gram128_launch(const pcs_wgrad_args &a, hipStream_t s);
+int pcs_gram_mirror_launch(float *G, int C, hipStream_t s);
 
 #define PCS_CHECK_LAUNCH()                                     \
   do {                                                         \

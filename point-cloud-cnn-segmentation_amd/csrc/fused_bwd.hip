@@ -663,72 +663,13 @@ int launch_bn(const pcs_gemm_args &a, float *wpart, int64_t rps, hipStream_t s) 
   return 0;
 }
 
-// (Cout, Cin) pairs served: (column block, rows per step).  The column-block split also
-// instantiates seg_conv3 (128 x 256, CB 128, 64-row steps) and seg_conv2 (256 x 512, CB 128,
-// 32-row steps: 64 spill VGPRs); both are correct (tests/test_gpu_fused_bwd.py history) but
-// measured no faster at cfg2 than the pcs_gemm + pcs_wgrad pair they replace (seg_conv3
-// 4.96 vs 4.73 ms, seg_conv2 12.8 vs 12.6 ms: 2 TB/s, latency-bound at one workgroup per
-// CU with the dy slab staged once per column block), so they stay on the pair.
-struct BnShape { int cout, cin, cb, ms; };
-// (seg_conv2 and seg_conv3 go to the LDS-DMA stream of fused_seg4.hip instead)
-constexpr BnShape kBnShapes[] = {{64, 64, 64, 64}, {128, 64, 64, 64}};
-
-const BnShape *bn_shape(int K, int Ncols) {
-  for (const BnShape &b : kBnShapes)
-    if (b.cout == K && b.cin == Ncols) return &b;
-  return nullptr;
-}
-
 }  // namespace
 
-extern "C" int64_t pcs_dgrad_wgrad_bn_workspace(pcs_gemm_args *a) {
-  if (!a || a->num_scenes <= 0 || a->scene_rows <= 0) return pcs_set_einval("pcs_dgrad_wgrad_bn_workspace", "bad geometry");
-  if (pcs_seg4_applicable(*a)) {   // seg_conv2 / seg_conv3: one wave per SIMD (fused_seg4.hip)
-    pcs_seg4_geometry(a);
-    return (int64_t)a->num_scenes * a->chunks_per_scene * a->K * a->Ncols * 4;
-  }
-  const BnShape *sh = bn_shape(a->K, a->Ncols);
-  if (a->dtype != PCS_BF16 || !sh || (a->flags & PCS_FLAG_GENERIC))
-    return pcs_set_einval("pcs_dgrad_wgrad_bn_workspace",
-                          "bf16 with (Cout, Cin) = K x Ncols in {64x64, 128x64} only");
-  const int nblk = sh->cin / sh->cb;
-  // 64 x 64 (conv2, conv3: <= 128 VGPRs) fits two 512-thread workgroups per CU: twice the
-  // workgroups, 0.91 -> 0.85 ms at cfg2; 128 x 64 (conv4, 158-164 VGPRs) stays at one
-  const int64_t target = sh->cout == 64 ? 512 : 256;
-  int64_t sps = (target + a->num_scenes * nblk - 1) / (a->num_scenes * nblk);
-  const int64_t max_sps = (a->scene_rows + 4 * sh->ms - 1) / (4 * sh->ms);
-  if (sps > max_sps) sps = max_sps;
-  if (sps < 1) sps = 1;
-  const int64_t rps = ((a->scene_rows + sps - 1) / sps + sh->ms - 1) / sh->ms * sh->ms;
-  a->chunks_per_scene = (int32_t)((a->scene_rows + rps - 1) / rps);   // no empty chunks
-  return (int64_t)a->num_scenes * a->chunks_per_scene * a->K * a->Ncols * 4;
-}
-
-extern "C" int pcs_dgrad_wgrad_bn(const pcs_gemm_args *ap, float *partial, float *dW, int64_t ldw,
-                                  pcs_stream_t stream) {
-  if (!ap || !partial || !dW) return pcs_set_einval("pcs_dgrad_wgrad_bn", "null argument");
-  pcs_gemm_args a = *ap;
-  if (pcs_dgrad_wgrad_bn_workspace(&a) < 0) return PCS_EINVAL;
-  if (a.chunks_per_scene != ap->chunks_per_scene)
-    return pcs_set_einval("pcs_dgrad_wgrad_bn", "chunks_per_scene must come from pcs_dgrad_wgrad_bn_workspace");
-  if (!a.A || !a.A2 || !a.pa || !a.pb || !a.pc || !a.W || !a.C || !a.Yp || !a.es || !a.et || !a.emean ||
-      !a.erstd || !a.stats)
-    return pcs_set_einval("pcs_dgrad_wgrad_bn", "missing operand (A, A2, pa, pb, pc, W, C, Yp, es, et, emean, "
-                                                "erstd, stats)");
-  if (a.scene_rows * a.num_scenes >= (int64_t)1 << 31) return pcs_set_einval("pcs_dgrad_wgrad_bn", "M must be < 2^31");
-  if (pcs_seg4_applicable(a)) {
-    const int rc = pcs_seg4_launch(a, partial, reinterpret_cast<hipStream_t>(stream));
-    if (rc) return rc;
-    const int nslab = (int)(a.num_scenes * a.chunks_per_scene);
-    return pcs_reduce_partials(partial, nslab, (int64_t)a.K * a.Ncols, 1.0f, dW, ldw ? ldw : a.Ncols, a.Ncols, stream);
-  }
-  const BnShape *sh = bn_shape(a.K, a.Ncols);
-  const int64_t rps = ((a.scene_rows + a.chunks_per_scene - 1) / a.chunks_per_scene + sh->ms - 1) / sh->ms * sh->ms;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc;
-  if (a.K == 64) rc = launch_bn<64, 64, 64, 64>(a, partial, rps, s);
-  else rc = launch_bn<128, 64, 64, 64>(a, partial, rps, s);
-  if (rc) return rc;
-  const int nslab = (int)(a.num_scenes * a.chunks_per_scene);
-  return pcs_reduce_partials(partial, nslab, (int64_t)a.K * a.Ncols, 1.0f, dW, ldw ? ldw : a.Ncols, a.Ncols, stream);
+// the instantiation for one of route.h's kBnShapes (pcs_dgrad_wgrad_bn, dispatch.hip)
+static_assert(route::bn_shape(64, 64)->cb == 64 && route::bn_shape(64, 64)->ms == 64 &&
+              route::bn_shape(128, 64)->cb == 64 && route::bn_shape(128, 64)->ms == 64 &&
+              sizeof(route::kBnShapes) / sizeof(route::kBnShapes[0]) == 2, "route.h");
+int pcs_dgrad_wgrad_bn_launch(const pcs_gemm_args &a, float *wpart, int64_t rps, hipStream_t s) {
+  if (a.K == 64) return launch_bn<64, 64, 64, 64>(a, wpart, rps, s);
+  return launch_bn<128, 64, 64, 64>(a, wpart, rps, s);
 }

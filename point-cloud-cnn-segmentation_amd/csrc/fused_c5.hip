@@ -23,6 +23,7 @@ namespace {
 constexpr int THREADS = 512;
 constexpr int MS = 32;                      // rows per step
 constexpr int K1 = 1024, K2 = 128, NC = 128;
+static_assert(K1 == route::C5_K1 && K2 == route::C5_K2 && NC == route::C5_NC, "route.h");
 constexpr int DZROW = K1 * 2;               // 2 KB dz5 row
 constexpr int YROW = K2 * 2;                // 256 B y4 row
 constexpr int DZB = MS * DZROW;             // 64 KB
@@ -281,18 +282,6 @@ __global__ __launch_bounds__(THREADS) void c5_dgrad_kernel(pcs_gemm_args a, int6
 }
 
 }  // namespace
-
-// conv5's folded input gradient: bf16, PCS_PRO_CAT with K1 = 1024, K - K1 = 128, 128 output
-// columns, EPI_DGRAD without dropout bits, addend or sparse pool rows.
-bool pcs_c5_dgrad_class(const pcs_gemm_args &a) {
-  return a.dtype == PCS_BF16 && !(a.flags & PCS_FLAG_GENERIC) && a.prologue == PCS_PRO_CAT &&
-         a.epilogue == PCS_EPI_DGRAD && a.K1 == K1 && a.K == K1 + K2 && a.Ncols == NC;
-}
-
-bool pcs_c5_dgrad_applicable(const pcs_gemm_args &a) {
-  return pcs_c5_dgrad_class(a) && !a.c_mask && !a.addend && !a.pool_w && a.A2 && a.W2 && a.pa && a.pb && a.C &&
-         a.Yp == a.A2 && (!a.erstd || a.emean);
-}
 
 int pcs_c5_dgrad_launch(const pcs_gemm_args &a, int64_t rows_per_chunk, hipStream_t s) {
   if (rows_per_chunk % MS != 0) return pcs_set_einval("pcs_gemm", "c5 dgrad: rows per chunk must be a multiple of 32");

@@ -37,6 +37,7 @@ namespace {
 constexpr int THREADS = 256;
 constexpr int CB = 256;   // CIN columns per workgroup
 constexpr int MS = 16;    // rows per step
+static_assert(CB == route::SEG4_CB && MS == route::SEG4_MS, "route.h");
 
 template <int COUT> struct S4 {
   static constexpr int NST = COUT == 256 ? 3 : 4;    // ring stages (NST - 1 steps in flight)
@@ -583,36 +584,9 @@ void seg4_kernel(pcs_gemm_args a, float *__restrict__ wpart, int64_t rows_per_sp
 
 }  // namespace
 
-// Shapes served: (Cout, Cin) = K x Ncols in {256 x 512 (seg_conv2), 128 x 256 (seg_conv3)}, bf16,
-// PRO_BWD / EPI_DGRAD, no addend.
-int64_t pcs_seg4_geometry(pcs_gemm_args *a);
-bool pcs_seg4_applicable(const pcs_gemm_args &a) {
-  if (!(a.dtype == PCS_BF16 && !(a.flags & PCS_FLAG_GENERIC) && !a.addend &&
-        ((a.K == 256 && a.Ncols == 512) || (a.K == 128 && a.Ncols == 256))))
-    return false;
-  // the buffer-store range and the per-lane row offsets are 32-bit: a slice's rows (Ncols
-  // bf16) below 2 GB
-  pcs_gemm_args g = a;
-  const int64_t rps = pcs_seg4_geometry(&g);
-  return rps * (int64_t)a.Ncols * 2 < ((int64_t)1 << 31);
-}
-
-int64_t pcs_seg4_geometry(pcs_gemm_args *a) {
-  const int nblk = a->Ncols / CB;
-  int64_t sps = (256 + a->num_scenes * nblk - 1) / (a->num_scenes * nblk);   // one WG per CU
-  const int64_t max_sps = (a->scene_rows + 8 * MS - 1) / (8 * MS);
-  if (sps > max_sps) sps = max_sps;
-  if (sps < 1) sps = 1;
-  const int64_t rps = ((a->scene_rows + sps - 1) / sps + MS - 1) / MS * MS;
-  a->chunks_per_scene = (int32_t)((a->scene_rows + rps - 1) / rps);   // no empty slices
-  return rps;
-}
-
-int pcs_seg4_launch(const pcs_gemm_args &a, float *wpart, hipStream_t s) {
-  pcs_gemm_args g = a;
-  const int64_t rps = pcs_seg4_geometry(&g);
-  if (g.chunks_per_scene != a.chunks_per_scene)
-    return pcs_set_einval("pcs_dgrad_wgrad_bn", "chunks_per_scene must come from pcs_dgrad_wgrad_bn_workspace");
+// Shapes served (route.h's bn_route): (Cout, Cin) = K x Ncols in {256 x 512 (seg_conv2), 128 x 256
+// (seg_conv3)}, bf16, PRO_BWD / EPI_DGRAD, no addend; rps = the route's rows per slice.
+int pcs_seg4_launch(const pcs_gemm_args &a, float *wpart, int64_t rps, hipStream_t s) {
   const int nb = (int)(a.num_scenes * a.chunks_per_scene) * (a.Ncols / CB);
 #define PCS_SEG4(CO, CI, MK) \
   hipLaunchKernelGGL((seg4_kernel<CO, CI, MK>), dim3(nb), dim3(THREADS), 0, s, a, wpart, rps)

@@ -50,9 +50,6 @@ template <> struct FsCfg<256, 128> {   // seg_conv3
 template <> struct FsCfg<128, 1024> {  // conv5 (BN5 + ReLU on the way out: a5)
   static constexpr int NB = 512, WCN = 8, MS = 64, NST = 4, TARGET = 256;
 };
-#ifndef FS_SMALL_TARGET
-#define FS_SMALL_TARGET 1024
-#endif
 template <> struct FsCfg<64, 128> {    // conv4
   static constexpr int NB = 128, WCN = 4, MS = 64, NST = 4, TARGET = FS_SMALL_TARGET;
 };
@@ -632,47 +629,22 @@ template <int K, int NC> struct FsShape {
   static bool is(const pcs_gemm_args &a) { return a.K == K && a.Ncols == NC; }
 };
 
+// route.h's table of the shapes served against the kernel's own configurations
+template <int K, int NC, int EPI> constexpr bool fs_routed() {
+  const route::FsShape *f = route::fs_shape(K, NC, EPI);
+  return f && f->nb == FsCfg<K, NC>::NB && f->target == FsCfg<K, NC>::TARGET;
+}
+static_assert(fs_routed<64, 512, PCS_EPI_FWD>() && fs_routed<512, 256, PCS_EPI_FWD>() &&
+              fs_routed<256, 128, PCS_EPI_FWD>() && fs_routed<64, 128, PCS_EPI_FWD>() &&
+              fs_routed<64, 64, PCS_EPI_FWD>() && fs_routed<128, 1024, PCS_EPI_BNRELU>() &&
+              sizeof(route::kFsShapes) / sizeof(route::kFsShapes[0]) == 6, "route.h");
+
 }  // namespace
 
-// Class (geometry, shapes only) and applicability (operands) of the streaming forward kernel.
-// bf16, PRO_BNRELU; EPI_FWD on (K, Ncols) = (64, 512) seg_conv1, (512, 256) seg_conv2, (256, 128)
-// seg_conv3, (64, 128) conv4, (64, 64) conv2 / conv3; EPI_BNRELU with a bf16 store on (128, 1024) conv5.
-template <int K, int NC> int fs_nb(int *target) {
-  if (target) *target = FsCfg<K, NC>::TARGET;
-  return FsCfg<K, NC>::NB;
-}
-int pcs_fwd_stream_nb(const pcs_gemm_args &a, int *target) {
-  if (a.dtype != PCS_BF16 || (a.flags & (PCS_FLAG_GENERIC | PCS_FLAG_AW_FP8)) || a.prologue != PCS_PRO_BNRELU)
-    return 0;
-  if (a.epilogue == PCS_EPI_FWD) {
-    if (FsShape<64, 512>::is(a)) return fs_nb<64, 512>(target);
-    if (FsShape<512, 256>::is(a)) return fs_nb<512, 256>(target);
-    if (FsShape<256, 128>::is(a)) return fs_nb<256, 128>(target);
-    if (FsShape<64, 128>::is(a)) return fs_nb<64, 128>(target);
-    if (FsShape<64, 64>::is(a)) return fs_nb<64, 64>(target);
-  } else if (a.epilogue == PCS_EPI_BNRELU) {
-    if (FsShape<128, 1024>::is(a)) return fs_nb<128, 1024>(target);
-  }
-  return 0;
-}
-
-bool pcs_fwd_stream_applicable(const pcs_gemm_args &a) {
-  if (!pcs_fwd_stream_nb(a, nullptr) || !a.C || !a.pa || !a.pb || a.pool) return false;
-  if ((a.flags & PCS_FLAG_C_FP8) && a.epilogue != PCS_EPI_BNRELU) return false;
-  if (a.scene_rows * a.num_scenes >= ((int64_t)1 << 31)) return false;
-  // 32-bit store ranges / row offsets: a chunk of the widest rows must stay below 2 GB
-  const int64_t rpc = a.chunks_per_scene > 0 ? (a.scene_rows + a.chunks_per_scene - 1) / a.chunks_per_scene
-                                             : a.scene_rows;
-  if (rpc * (int64_t)(a.K > a.Ncols ? a.K : a.Ncols) * 2 >= ((int64_t)1 << 31)) return false;
-  if (a.epilogue == PCS_EPI_BNRELU) return a.es && a.et && !a.a_mask && !a.scene_bias;
-  // dropout bits only where the layer has them (seg_conv2 / seg_conv3 inputs)
-  if (a.a_mask && !(FsShape<512, 256>::is(a) || FsShape<256, 128>::is(a))) return false;
-  if (a.scene_bias && !FsShape<64, 512>::is(a)) return false;
-  return true;
-}
-
 int pcs_fwd_stream_launch(const pcs_gemm_args &a, int64_t rows_per_chunk, hipStream_t s) {
-  const int nb_cols = pcs_fwd_stream_nb(a, nullptr);
+  const route::FsShape *f = route::fwd_stream_shape(a);
+  if (!f) return pcs_set_einval("pcs_gemm", "streaming forward: unsupported shape");
+  const int nb_cols = f->nb;
   const int nb = (int)(a.num_scenes * a.chunks_per_scene) * (a.Ncols / nb_cols);
 #define PCS_FS(K, NC, EPI, MK, SB) \
   hipLaunchKernelGGL((fwd_stream_kernel<K, NC, EPI, MK, SB>), dim3(nb), dim3(THREADS), 0, s, a, rows_per_chunk)

@@ -27,6 +27,7 @@ namespace {
 constexpr int THREADS = 512;
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int KMAX = 1024;                   // per-channel coefficient arrays live in LDS
+static_assert(BM == route::BIG_BM && BN == route::BIG_BN && BK == route::BIG_BK && KMAX == route::KMAX, "route.h");
 constexpr int ROWB = BK * 2;                 // 128 B per LDS row
 constexpr int STAGE = (BM + BN) * ROWB;      // 64 KB
 constexpr int CROW = BN * 2 + 16;            // epilogue tile row stride
@@ -504,18 +505,6 @@ int launch(const pcs_gemm_args &a, int tps, int tpc, hipStream_t s) {
 }
 
 }  // namespace
-
-bool pcs_gemm_big_applicable(const pcs_gemm_args &a) {
-  if (a.dtype != PCS_BF16 || a.K % BK != 0 || a.Ncols % BN != 0 || a.K < 128 || a.K > KMAX) return false;
-  if (a.flags & PCS_FLAG_GENERIC) return false;
-  if (a.a_mask && a.prologue != PCS_PRO_BNRELU) return false;
-  if (a.epilogue == PCS_EPI_FWD || a.epilogue == PCS_EPI_BNRELU)
-    return a.prologue == PCS_PRO_BNRELU || a.prologue == PCS_PRO_RAW;
-  if (a.epilogue == PCS_EPI_DGRAD && (!a.es || !a.erstd || a.bias || a.pool_w)) return false;
-  if (a.epilogue == PCS_EPI_DGRAD) return a.prologue == PCS_PRO_BWD && !(a.c_mask && a.addend);
-  if (a.epilogue == PCS_EPI_RAW) return a.prologue == PCS_PRO_BWD;
-  return false;
-}
 
 int pcs_gemm_big_launch(const pcs_gemm_args &g, int tps, int tpc, hipStream_t s) {
   switch (g.epilogue) {

@@ -18,6 +18,7 @@ namespace {
 
 constexpr int THREADS = 512;
 constexpr int TM = 256, TN = 256, MS = 64;
+static_assert(TM == route::BIGTN_TM && TN == route::BIGTN_TN && MS == route::BIGTN_MS, "route.h");
 constexpr int ROWB = TM * 2 + 32;          // 544 B: padded LDS row
 constexpr int OPB = MS * ROWB;             // one operand tile (34 KB)
 constexpr int STAGE = 2 * OPB;
@@ -257,40 +258,9 @@ __global__ __launch_bounds__(THREADS) void wgrad_big_kernel(pcs_wgrad_args a, in
 
 }  // namespace
 
-bool pcs_wgrad_big_applicable(const pcs_wgrad_args &a) {
-  if (a.dy_mode == PCS_PRO_BNRELU && (a.Cout != a.Cin || a.x_mask)) return false;   // Gram: square
-  return !(a.flags & PCS_FLAG_GENERIC) && a.dtype == PCS_BF16 && a.Cout % TM == 0 && a.Cin % TN == 0 &&
-         a.x_mode == PCS_PRO_BNRELU &&
-         (a.dy_mode == PCS_PRO_BWD || a.dy_mode == PCS_PRO_BNRELU);
-}
-
-int pcs_wgrad_big_tiles(const pcs_wgrad_args &a) {
-  const int ntm = a.Cout / TM, ntn = a.Cin / TN;
-  return a.dy_mode == PCS_PRO_BNRELU ? ntm * (ntm + 1) / 2 : ntm * ntn;
-}
-
-int pcs_wgrad_big_splits(const pcs_wgrad_args &a) {
-  // one 512-thread workgroup per CU: pick the row splits per scene that minimise
-  // (waves of 256 workgroups) / splits, i.e. the time of the slowest CU, with the fp32
-  // partial slabs kept below 256 MB
-  const int64_t per_split = a.num_scenes * pcs_wgrad_big_tiles(a);
-  const int64_t slab = (int64_t)a.Cout * a.Cin * 4;
-  const int64_t max_sps = pcs_max64(1, pcs_min64((a.scene_rows + 8 * MS - 1) / (8 * MS),
-                                                 ((int64_t)256 << 20) / slab / a.num_scenes));
-  int64_t best = 1;
-  double best_cost = 1e30;
-  for (int64_t sps = 1; sps <= max_sps; ++sps) {
-    const double waves = (double)((per_split * sps + 255) / 256);
-    const double cost = waves / (double)sps * (1.0 + 1e-3 * sps);   // tie-break: fewer slabs
-    if (cost < best_cost) { best_cost = cost; best = sps; }
-  }
-  return (int)best;
-}
-
 int pcs_wgrad_big_launch(const pcs_wgrad_args &a, hipStream_t s) {
-  int64_t rps = (a.scene_rows + a.splits_per_scene - 1) / a.splits_per_scene;
-  rps = (rps + MS - 1) / MS * MS;
-  const int ntn = a.Cin / TN, ntiles = pcs_wgrad_big_tiles(a);
+  const int64_t rps = route::rows_per_split(a.scene_rows, a.splits_per_scene, MS);
+  const int ntn = a.Cin / TN, ntiles = route::wgrad_big_tiles(a);
   const int nb = ntiles * (int)(a.num_scenes * a.splits_per_scene);
   if (a.dy_mode == PCS_PRO_BNRELU) {
     if (!a.s)   // Gram of stored activations (pcs_gram with s = t = NULL)

@@ -35,6 +35,7 @@ namespace {
 
 constexpr int THREADS = 512;
 constexpr int BM = 256, BN = 256, BK = 64;
+static_assert(BM == route::BIG_BM && BN == route::BIG_BN && BK == route::BIG_BK, "route.h");
 constexpr int REG = 128 * BK * 2;                  // one region: 128 rows x 128 B
 constexpr int KBUF = 4 * REG;                      // A-lo | A-hi | B-lo | B-hi
 constexpr int STAGE_BYTES = 2 * KBUF;              // 128 KB
@@ -734,22 +735,6 @@ __global__ __launch_bounds__(THREADS) void gemm_glds_kernel(pcs_gemm_args a, int
 }
 
 }  // namespace
-
-bool pcs_gemm_glds_applicable(const pcs_gemm_args &a) {
-  if (a.dtype != PCS_BF16 || (a.flags & (PCS_FLAG_GENERIC | PCS_FLAG_NO_GLDS))) return false;
-  const bool fp8 = a.flags & PCS_FLAG_AW_FP8;
-  if (fp8 && !a.w_scale) return false;
-  if (a.prologue != PCS_PRO_RAW || a.K % (fp8 ? 256 : 2 * BK) != 0 || a.Ncols % BN != 0) return false;
-  // forward: statistics / max-pool only (nothing stored); the pool keeps one extremum per
-  // column, chosen by sign(es), so a pool needs es
-  if (a.epilogue == PCS_EPI_FWD)
-    return a.C == nullptr && a.scene_bias == nullptr && (!a.pool || a.es) &&
-           (!(a.flags & PCS_FLAG_POOL_SIGNED_W) || (a.pool && !a.stats));
-  if (a.epilogue == PCS_EPI_DGRAD)   // mask read from the operand itself, no S2, no addend
-    return a.Yp == a.A && a.K == a.Ncols && !a.es && !a.et && !a.erstd && !a.addend && !a.c_mask &&
-           !a.pool_w;
-  return false;
-}
 
 int pcs_gemm_glds_launch(const pcs_gemm_args &g, int tps, int tpc, hipStream_t s) {
   const int ncb = g.Ncols / BN;

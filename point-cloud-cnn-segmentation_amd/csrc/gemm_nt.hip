@@ -52,6 +52,7 @@ template <> struct Mfma<float> {
 };
 
 constexpr int KMAX = 1024;   // prologue coefficient arrays staged in LDS (K <= KMAX)
+static_assert(KMAX == route::KMAX, "route.h");
 
 template <int PRO> struct Coef {   // per-channel prologue arrays kept in LDS
   static constexpr int N = (PRO == PCS_PRO_BNRELU || PRO == PCS_PRO_CAT) ? 2 : PRO == PCS_PRO_BWD ? 3 : 0;
@@ -509,6 +510,7 @@ int launch_t(const pcs_gemm_args &a, int tps, int tpc, hipStream_t s) {
 template <typename T, int BN>
 int dispatch_pro_epi(const pcs_gemm_args &a, int tps, int tpc, hipStream_t s) {
   constexpr int BM = 128;
+  static_assert(BM == route::NT_BM, "route.h");
   const bool pool = a.pool != nullptr;
   switch (a.epilogue) {
     case PCS_EPI_FWD:
@@ -556,109 +558,8 @@ int dispatch_pro_epi(const pcs_gemm_args &a, int tps, int tpc, hipStream_t s) {
 
 }  // namespace
 
-static constexpr int GEMM_BM = 128;
-
-// The row-chunk geometry depends only on shapes, dtype and flags, never on which optional
-// operands are set: callers size their partial buffers from pcs_gemm_geometry() before the
-// pointers exist.  Shapes the 256x256 kernels can take use 256-row-multiple chunks; if a call
-// of that class ends up on the generic kernel (an operand combination the wide kernels do not
-// implement), that kernel walks the same chunks in 128-row tiles.
-static bool wide_class(const pcs_gemm_args &a) {
-  if (a.prologue == PCS_PRO_CAT) return false;   // generic kernel only
-  // seg_conv3's input gradient (K 128 -> 256 columns, DGRAD epilogue): the 128-row kernel
-  // measured faster at cfg2 (3.13 vs 3.38 ms, tools/bench_bwd_shapes.py)
-  if (a.K == 128 && a.Ncols == 256 && a.epilogue == PCS_EPI_DGRAD) return false;
-  return a.dtype == PCS_BF16 && !(a.flags & PCS_FLAG_GENERIC) && a.K % 64 == 0 && a.Ncols % 256 == 0 &&
-         a.K >= 128 && a.K <= 1024;
-}
-
-extern "C" int64_t pcs_gemm_geometry(pcs_gemm_args *a) {
-  if (!a || a->num_scenes <= 0 || a->scene_rows <= 0 || a->Ncols <= 0)
-    return pcs_set_einval("pcs_gemm_geometry", "empty geometry");
-  int fs_target = 256;
-  if (const int nbc = pcs_fwd_stream_nb(*a, &fs_target))   // streaming forward
-    return pcs_fill_geometry(a, 256, fs_target, a->Ncols / nbc);
-  if (wide_class(*a))
-    return pcs_fill_geometry(a, PCS_BIG_BM, 256, a->Ncols / 256);   // one 512-thread WG per CU
-  if (pcs_c5_dgrad_class(*a))   // conv5's folded input gradient: one 512-thread WG per CU
-    return pcs_fill_geometry(a, GEMM_BM, 256, 1);
-  const int64_t ncb = a->Ncols >= 128 ? a->Ncols / 128 : 1;
-  return pcs_fill_geometry(a, GEMM_BM, 2048, ncb);                 // ~8 WGs per CU
-}
-
-extern "C" int pcs_gemm(const pcs_gemm_args *ap, pcs_stream_t stream) {
-  if (!ap) return pcs_set_einval("pcs_gemm", "null args");
-  pcs_gemm_args a = *ap;
-  if (a.prologue != PCS_PRO_RAW && a.prologue != PCS_PRO_BNRELU && a.prologue != PCS_PRO_BWD &&
-      a.prologue != PCS_PRO_CAT)
-    return pcs_set_einval("pcs_gemm", "unknown prologue (PCS_PRO_RAW, PCS_PRO_BNRELU, PCS_PRO_BWD or PCS_PRO_CAT)");
-  if (a.K <= 0 || a.Ncols <= 0) return pcs_set_einval("pcs_gemm", "K/Ncols must be positive");
-  if (a.Ncols % 64 != 0) return pcs_set_einval("pcs_gemm", "Ncols must be a multiple of 64");
-  const int kstep = a.dtype == PCS_BF16 ? 32 : 16;
-  if (a.K % kstep != 0) return pcs_set_einval("pcs_gemm", "K must be a multiple of the k-step");
-  if (!a.A || !a.W) return pcs_set_einval("pcs_gemm", "A and W are required");
-  if (a.prologue == PCS_PRO_BWD && (!a.A2 || !a.pa || !a.pb || !a.pc))
-    return pcs_set_einval("pcs_gemm", "PRO_BWD needs A2 (=Y_l), alpha, beta, gamma");
-  if (a.prologue == PCS_PRO_BNRELU && (!a.pa || !a.pb))
-    return pcs_set_einval("pcs_gemm", "PRO_BNRELU needs s and t");
-  if (a.epilogue < PCS_EPI_FWD || a.epilogue > PCS_EPI_BNRELU) return pcs_set_einval("pcs_gemm", "bad epilogue");
-  if (a.epilogue == PCS_EPI_DGRAD && (!a.Yp || !a.C || !a.es != !a.et || (a.erstd && !a.emean)))
-    return pcs_set_einval("pcs_gemm", "EPI_DGRAD needs Yp and C (es/et both or neither, emean with erstd)");
-  if (a.epilogue == PCS_EPI_BNRELU && (!a.es || !a.et || !a.C || a.pool))
-    return pcs_set_einval("pcs_gemm", "EPI_BNRELU needs es, et and C (no pool)");
-  // EPI_BNRELU statistics = per-chunk column sums of the stored output (bf16 256-wide kernel)
-  if (a.epilogue == PCS_EPI_BNRELU && a.stats &&
-      !(wide_class(a) && (pcs_gemm_wres_applicable(a) || pcs_gemm_big_applicable(a))))
-    return pcs_set_einval("pcs_gemm", "EPI_BNRELU column sums need the bf16 256-wide kernel (Ncols % 256 == 0)");
-  if (a.pool && a.epilogue != PCS_EPI_FWD) return pcs_set_einval("pcs_gemm", "pool needs EPI_FWD");
-  if (a.pool_w && (a.epilogue != PCS_EPI_DGRAD || a.prologue != PCS_PRO_RAW || !a.pool_idx || !a.pool_coef ||
-                   a.pool_c <= 0 || a.pool_c > 1024 || a.pool_ldw < a.Ncols))
-    return pcs_set_einval("pcs_gemm", "pool_w (sparse rows) needs EPI_DGRAD, PRO_RAW, pool_idx, pool_coef, "
-                                      "0 < pool_c <= 1024, pool_ldw >= Ncols");
-  if (a.scene_rows * a.num_scenes >= (int64_t)1 << 31)
-    return pcs_set_einval("pcs_gemm", "M must be < 2^31 rows");
-  if (a.prologue == PCS_PRO_CAT) {
-    if (!a.A2 || !a.W2 || !a.pa || !a.pb || a.K1 <= 0 || a.K1 >= a.K || a.K1 % kstep || a.K - a.K1 > KMAX ||
-        a.epilogue != PCS_EPI_DGRAD || a.a_mask)
-      return pcs_set_einval("pcs_gemm", "PRO_CAT needs A2, W2, pa, pb, 0 < K1 < K (a k-step multiple), "
-                                        "K - K1 <= 1024, EPI_DGRAD, no a_mask");
-  } else if (a.K > KMAX) {
-    return pcs_set_einval("pcs_gemm", "K must be <= 1024");
-  }
-  if ((a.flags & PCS_FLAG_AW_FP8) && !(wide_class(a) && pcs_gemm_glds_applicable(a)))
-    return pcs_set_einval("pcs_gemm", "fp8 operands (PCS_FLAG_AW_FP8) need the LDS-DMA kernel: bf16 C, RAW prologue, "
-                                      "K % 256 == 0, Ncols % 256 == 0, w_scale, FWD (no C) or folded DGRAD");
-  if ((a.flags & PCS_FLAG_C_FP8) && !(a.epilogue == PCS_EPI_BNRELU &&
-                                      (a.prologue == PCS_PRO_BNRELU || a.prologue == PCS_PRO_RAW) && !a.a_mask &&
-                                      wide_class(a) && (pcs_gemm_wres_applicable(a) || pcs_gemm_big_applicable(a))))
-    return pcs_set_einval("pcs_gemm", "fp8 output (PCS_FLAG_C_FP8) needs PRO_BNRELU (no dropout) or PRO_RAW + EPI_BNRELU "
-                                      "on the bf16 256-wide kernel");
-  if ((a.flags & PCS_FLAG_POOL_SIGNED_W) && !(a.epilogue == PCS_EPI_FWD && a.pool && a.es && !a.stats &&
-                                             wide_class(a) && pcs_gemm_glds_applicable(a)))
-    return pcs_set_einval("pcs_gemm", "PCS_FLAG_POOL_SIGNED_W needs EPI_FWD with pool and es, no statistics, on the "
-                                      "LDS-DMA kernel");
-  if (a.a_mask && a.prologue != PCS_PRO_BNRELU)
-    return pcs_set_einval("pcs_gemm", "a_mask applies to the BNRELU prologue only");
-  const int64_t rpc = pcs_gemm_geometry(&a);
-  if (rpc < 0) return (int)rpc;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (a.gram && !(a.K == 64 && a.Ncols == 64 && a.epilogue == PCS_EPI_FWD && !a.a_mask && !a.scene_bias &&
-                  pcs_fwd_stream_applicable(a)))
-    return pcs_set_einval("pcs_gemm", "gram (the operand's Gram) needs bf16 PRO_BNRELU + EPI_FWD, K = Ncols = 64, "
-                                      "no dropout bits, on the streaming kernel");
-  if (pcs_fwd_stream_applicable(a)) return pcs_fwd_stream_launch(a, rpc, s);
-  if (wide_class(a) && pcs_gemm_wres_applicable(a)) return pcs_gemm_wres_launch(a, rpc, s);
-  if (wide_class(a) && pcs_gemm_glds_applicable(a)) {
-    const int tps = (int)((a.scene_rows + PCS_BIG_BM - 1) / PCS_BIG_BM);
-    return pcs_gemm_glds_launch(a, tps, (int)(rpc / PCS_BIG_BM), s);
-  }
-  if (wide_class(a) && pcs_gemm_big_applicable(a)) {
-    const int tps = (int)((a.scene_rows + PCS_BIG_BM - 1) / PCS_BIG_BM);
-    return pcs_gemm_big_launch(a, tps, (int)(rpc / PCS_BIG_BM), s);
-  }
-  if (pcs_c5_dgrad_applicable(a)) return pcs_c5_dgrad_launch(a, rpc, s);
-  const int tps = (int)((a.scene_rows + GEMM_BM - 1) / GEMM_BM);
-  const int tpc = (int)(rpc / GEMM_BM);
+// the generic kernel's instantiation for a dtype and column block (pcs_gemm, dispatch.hip)
+int pcs_gemm_nt_launch(const pcs_gemm_args &a, int tps, int tpc, hipStream_t s) {
   const bool bn128 = a.Ncols % 128 == 0;
   if (a.dtype == PCS_BF16)
     return bn128 ? dispatch_pro_epi<bf16_t, 128>(a, tps, tpc, s) : dispatch_pro_epi<bf16_t, 64>(a, tps, tpc, s);

@@ -31,6 +31,8 @@ template <> struct TnCfg<float> {
   static PCS_DEV int prow(int r) { return r; }
 };
 
+static_assert(TnCfg<bf16_t>::MS == route::TN_MS_BF16 && TnCfg<float>::MS == route::TN_MS_F32, "route.h");
+
 template <typename T, int COLS, int MODE>
 struct Operand {
   // staging of one [MS x COLS] operand tile; a thread owns a fixed column chunk
@@ -302,79 +304,6 @@ int dispatch_tiles(const pcs_wgrad_args &a, int64_t rps, hipStream_t s) {
   return dispatch_modes<T, 64, 64>(a, rps, s);
 }
 
-int64_t rows_per_split_of(const pcs_wgrad_args &a, int ms) {
-  const int64_t rps = (a.scene_rows + a.splits_per_scene - 1) / a.splits_per_scene;
-  return (rps + ms - 1) / ms * ms;
-}
-
-// a caller built against ABI 2 may still fill the three fields ABI 3 removed (pcs.h)
-bool reserved_set(const pcs_wgrad_args &a) { return a.reserved0 || a.reserved1 || a.reserved2; }
-
-}  // namespace
-
-extern "C" int64_t pcs_wgrad_workspace(pcs_wgrad_args *a) {
-  if (!a || a->num_scenes <= 0 || a->scene_rows <= 0 || a->Cout <= 0 || a->Cin <= 0)
-    return pcs_set_einval("pcs_wgrad_workspace", "bad geometry");
-  if (reserved_set(*a)) return pcs_set_einval("pcs_wgrad_workspace", "reserved0..2 must be NULL (removed in ABI 3)");
-  const int ms = a->dtype == PCS_BF16 ? TnCfg<bf16_t>::MS : TnCfg<float>::MS;
-  if (a->splits_per_scene <= 0 && pcs_wgrad_c5_class(*a)) a->splits_per_scene = pcs_wgrad_c5_splits(*a);
-  if (a->splits_per_scene <= 0 && pcs_wgrad_big_applicable(*a)) a->splits_per_scene = pcs_wgrad_big_splits(*a);
-  if (a->splits_per_scene <= 0) {
-    const int tm = a->Cout % 128 == 0 ? 128 : 64, tn = a->Cin % 128 == 0 ? 128 : 64;
-    const int64_t ntiles = a->Cin >= 64 ? (int64_t)(a->Cout / tm) * (a->Cin / tn) : 1;
-    const int64_t target = 1024;
-    int64_t sps = (target + a->num_scenes * ntiles - 1) / (a->num_scenes * ntiles);
-    const int64_t max_sps = (a->scene_rows + 4 * ms - 1) / (4 * ms);  // >= 4 steps per split
-    if (sps > max_sps) sps = max_sps;
-    if (sps < 1) sps = 1;
-    a->splits_per_scene = (int32_t)sps;
-  }
-  const int64_t nslabs = (int64_t)a->num_scenes * a->splits_per_scene;
-  return nslabs * a->Cout * a->Cin * 4;
-}
-
-extern "C" int pcs_wgrad(const pcs_wgrad_args *ap, pcs_stream_t stream) {
-  if (!ap) return pcs_set_einval("pcs_wgrad", "null args");
-  pcs_wgrad_args a = *ap;
-  if (reserved_set(a)) return pcs_set_einval("pcs_wgrad", "reserved0..2 must be NULL (removed in ABI 3)");
-  if (a.dy_mode != PCS_PRO_RAW && a.dy_mode != PCS_PRO_BNRELU && a.dy_mode != PCS_PRO_BWD)
-    return pcs_set_einval("pcs_wgrad", "unknown dy_mode (PCS_PRO_RAW, PCS_PRO_BNRELU or PCS_PRO_BWD)");
-  if (a.Cout % 64 || a.Cin % 64) return pcs_set_einval("pcs_wgrad", "Cout/Cin must be multiples of 64");
-  if (!a.X || !a.partial || !a.dW) return pcs_set_einval("pcs_wgrad", "missing operand");
-  if (a.dy_mode == PCS_PRO_RAW ? !a.dZ : (!a.Y || !a.beta || !a.gamma))
-    return pcs_set_einval("pcs_wgrad", "dy operands missing (RAW: dZ; otherwise: Y, beta, gamma)");
-  if (a.dy_mode == PCS_PRO_BWD && (!a.dZ || !a.alpha)) return pcs_set_einval("pcs_wgrad", "PRO_BWD needs dZ, alpha");
-  if (a.x_mode == PCS_PRO_BNRELU && (!a.s || !a.t)) return pcs_set_einval("pcs_wgrad", "x BNRELU needs s, t");
-  if (pcs_wgrad_workspace(&a) < 0) return PCS_EINVAL;
-  const int ms = a.dtype == PCS_BF16 ? TnCfg<bf16_t>::MS : TnCfg<float>::MS;
-  const int64_t rps = rows_per_split_of(a, ms);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  int rc;
-  if (pcs_wgrad_c5_applicable(a)) rc = pcs_wgrad_c5_launch(a, rps, s);
-  else if (pcs_wgrad_big_applicable(a)) rc = pcs_wgrad_big_launch(a, s);
-  else if (a.dtype == PCS_BF16) rc = dispatch_tiles<bf16_t>(a, rps, s);
-  else if (a.dtype == PCS_F32) rc = dispatch_tiles<float>(a, rps, s);
-  else return pcs_set_einval("pcs_wgrad", "bad dtype");
-  if (rc) return rc;
-  const int64_t nslabs = a.num_scenes * a.splits_per_scene;
-  return pcs_reduce_partials(a.partial, nslabs, (int64_t)a.Cout * a.Cin, 1.0f, a.dW,
-                             a.ldw ? a.ldw : a.Cin, a.Cin, stream);
-}
-
-// ---------------------------------------------------------------------------------------
-// Gram of the BN+ReLU activations (global_feat weight gradient, see gram.hip)
-// ---------------------------------------------------------------------------------------
-namespace {
-
-pcs_wgrad_args gram_args(const void *Y, const float *s, const float *t, int64_t num_scenes,
-                         int64_t scene_rows, int32_t C, int32_t dtype, int32_t sps) {
-  pcs_wgrad_args a = {};
-  a.num_scenes = num_scenes; a.scene_rows = scene_rows; a.Cout = C; a.Cin = C; a.dtype = dtype;
-  a.splits_per_scene = sps; a.dy_mode = PCS_PRO_BNRELU; a.x_mode = PCS_PRO_BNRELU;
-  a.Y = Y; a.X = Y; a.s = s; a.t = t; a.x_keep_scale = 1.f;
-  return a;
-}
-
 // Mirror the upper 64x64 tiles of the summed Gram into the lower ones (the 256x256 kernel
 // computes only upper tiles; a transposed copy through LDS keeps both sides coalesced).
 __global__ __launch_bounds__(256) void gram_mirror_kernel(float *__restrict__ G, int C) {
@@ -391,49 +320,18 @@ __global__ __launch_bounds__(256) void gram_mirror_kernel(float *__restrict__ G,
 
 }  // namespace
 
-extern "C" int64_t pcs_gram_workspace(int64_t num_scenes, int64_t scene_rows, int32_t C, int32_t dtype,
-                                      int32_t *splits_per_scene) {
-  if (num_scenes <= 0 || scene_rows <= 0 || C <= 0 || C % 64 || !splits_per_scene)
-    return pcs_set_einval("pcs_gram_workspace", "bad geometry");
-  pcs_wgrad_args a = gram_args(nullptr, nullptr, nullptr, num_scenes, scene_rows, C, dtype, 0);
-  if (pcs_gram128_class(a)) a.splits_per_scene = pcs_gram128_splits(a);
-  const int64_t g = pcs_wgrad_workspace(&a);
-  if (g < 0) return g;
-  *splits_per_scene = a.splits_per_scene;
-  return g + num_scenes * a.splits_per_scene * (int64_t)C * 4;
+// the generic kernel's instantiation for a dtype and the tile sizes (pcs_wgrad, pcs_gram: dispatch.hip)
+int pcs_wgrad_tn_launch(const pcs_wgrad_args &a, int64_t rps, hipStream_t s) {
+  if (a.dtype == PCS_BF16) return dispatch_tiles<bf16_t>(a, rps, s);
+  if (a.dtype == PCS_F32) return dispatch_tiles<float>(a, rps, s);
+  return pcs_set_einval("pcs_wgrad", "bad dtype");
 }
 
-extern "C" int pcs_gram(const void *Y, const float *s, const float *t, int64_t num_scenes, int64_t scene_rows,
-                        int32_t C, int32_t dtype, int32_t splits_per_scene, float *workspace, float *G,
-                        float *colsum, pcs_stream_t stream) {
-  if (!Y || !s != !t || !workspace || !G || !colsum || splits_per_scene <= 0)
-    return pcs_set_einval("pcs_gram", "missing operand or splits (s and t both set, or both NULL)");
-  if (C % 64) return pcs_set_einval("pcs_gram", "C must be a multiple of 64");
-  pcs_wgrad_args a = gram_args(Y, s, t, num_scenes, scene_rows, C, dtype, splits_per_scene);
-  a.partial = workspace;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int rc;
-  if (!s && !pcs_wgrad_big_applicable(a))   // s = t = NULL: Y is already the activation
-    return pcs_set_einval("pcs_gram", "s = t = NULL needs the 256x256 kernel (bf16, C % 256 == 0)");
-  if (pcs_gram128_applicable(a)) {
-    rc = pcs_gram128_launch(a, st);
-  } else if (pcs_wgrad_big_applicable(a)) {
-    rc = pcs_wgrad_big_launch(a, st);
-  } else {
-    const int ms = dtype == PCS_BF16 ? TnCfg<bf16_t>::MS : TnCfg<float>::MS;
-    const int64_t rps = rows_per_split_of(a, ms);
-    if (dtype == PCS_BF16) rc = dispatch_tiles<bf16_t>(a, rps, st);
-    else if (dtype == PCS_F32) rc = dispatch_tiles<float>(a, rps, st);
-    else return pcs_set_einval("pcs_gram", "bad dtype");
-  }
-  if (rc) return rc;
-  const int nsplit = (int)(num_scenes * splits_per_scene);
-  const int64_t n = (int64_t)C * C;
-  if ((rc = pcs_reduce_partials(workspace, nsplit, n, 1.f, G, C, C, stream))) return rc;
-  if ((rc = pcs_reduce_partials(workspace + nsplit * n, nsplit, C, 1.f, colsum, C, C, stream))) return rc;
+// pcs_gram's last step (global_feat weight gradient, see gram.hip)
+int pcs_gram_mirror_launch(float *G, int C, hipStream_t s) {
   const int nt = C / 64;
   if (nt > 1) {
-    hipLaunchKernelGGL(gram_mirror_kernel, dim3(nt * (nt - 1) / 2), dim3(256), 0, st, G, C);
+    hipLaunchKernelGGL(gram_mirror_kernel, dim3(nt * (nt - 1) / 2), dim3(256), 0, s, G, C);
     PCS_CHECK_LAUNCH();
   }
   return 0;

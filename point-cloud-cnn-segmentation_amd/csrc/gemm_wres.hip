@@ -6,7 +6,7 @@
 // At K = 128 the work per output element is small (256 FLOP per 2 or 1 stored bytes); the
 // register-staged 256x256 kernel (gemm_big.hip), which drains its pipeline into an LDS tile at
 // every epilogue, ran the fp8 form at 2.2 TB/s.  Here (used for the fp8 store; see
-// pcs_gemm_wres_applicable for the bf16 measurement):
+// route.h's gemm_wres_takes for the bf16 measurement):
 // * a workgroup owns 256 output columns for its whole row chunk: that 256 x 128 block of W is
 //   loaded into LDS once (64 KB, XOR-swizzled 16-B slots) and stays there;
 // * y4 streams through a 5-stage LDS ring of 64-row tiles by LDS-DMA
@@ -35,6 +35,7 @@ namespace {
 constexpr int THREADS = 512;
 constexpr int K = 128;                  // conv5's input width
 constexpr int BMW = 64, BNW = 256;      // row tile, column block
+static_assert(K == route::WRES_K && BNW == route::WRES_BN, "route.h");
 constexpr int NSTAGE = 5;               // A ring depth
 constexpr int ROWB = K * 2;             // 256 B per LDS row (W and A)
 constexpr int W_BYTES = BNW * ROWB;     // 64 KB
@@ -364,16 +365,6 @@ __global__ __launch_bounds__(THREADS) void wres_bnrelu_kernel(pcs_gemm_args a, i
 }
 
 }  // namespace
-
-// Measured at cfg2 (tools/bench_conv5.py): fp8 store 4.0 ms here vs 4.9 ms on the
-// register-staged kernel; bf16 store 5.4 vs 5.0 ms, so bf16 stays there (the pass is bound by
-// the epilogue's vector work and the store issue, not by the MFMAs or the loads).
-bool pcs_gemm_wres_applicable(const pcs_gemm_args &a) {
-  if (a.dtype != PCS_BF16 || (a.flags & (PCS_FLAG_GENERIC | PCS_FLAG_NO_GLDS | PCS_FLAG_AW_FP8))) return false;
-  if (!(a.flags & PCS_FLAG_C_FP8)) return false;
-  return a.prologue == PCS_PRO_BNRELU && a.epilogue == PCS_EPI_BNRELU && a.K == K && a.Ncols % BNW == 0 &&
-         !a.a_mask && a.C && a.es && a.et && !a.pool && !a.scene_bias && a.scene_rows * a.num_scenes < ((int64_t)1 << 31);
-}
 
 // geometry: the caller's chunks (multiples of 256 rows, pcs_gemm_geometry) in 128-row tiles
 int pcs_gemm_wres_launch(const pcs_gemm_args &g, int64_t rows_per_chunk, hipStream_t s) {

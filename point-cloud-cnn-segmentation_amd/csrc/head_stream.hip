@@ -22,6 +22,7 @@ constexpr int THREADS = 512;
 constexpr int CIN = 128;
 constexpr int ROWB = CIN * 2;          // 256-B y rows
 constexpr int MS = 64;                 // rows per step (8 per wave)
+static_assert(CIN == route::HS_CIN && MS == route::HS_MS, "route.h");
 constexpr int WR = 8;                  // rows per wave per step
 constexpr int YW = WR * ROWB;          // 2 KB of y per wave per step
 constexpr int WAVEB = YW + WR * 8;     // + 64 B of labels
@@ -232,17 +233,6 @@ __global__ __launch_bounds__(THREADS, (C <= 2 ? HS_WPS : 1)) void head_stream_ke
 }
 
 }  // namespace
-
-// bf16, CE mode, C <= 4, no logits out (the fused train step); shapes / modes only
-bool pcs_head_stream_class(const pcs_head_args &a) {
-  return a.dtype == PCS_BF16 && a.mode == PCS_HEAD_CE && a.num_classes >= 1 && a.num_classes <= 4 &&
-         !a.logits && a.Cin == CIN && a.num_scenes * a.scene_rows < ((int64_t)1 << 31);
-}
-
-#ifndef HS_TARGET
-#define HS_TARGET 1024
-#endif
-int pcs_head_stream_target() { return HS_TARGET; }
 
 int pcs_head_stream_launch(const pcs_head_args &a, int64_t rows_per_chunk, hipStream_t s) {
   if (rows_per_chunk % MS) return pcs_set_einval("pcs_head", "stream head: rows per chunk must be a multiple of 64");

@@ -1338,10 +1338,9 @@ extern "C" int pcs_pool_bwd(const pcs_pool_bwd_args *ap, pcs_stream_t stream) {
 
 extern "C" int64_t pcs_head_geometry(pcs_head_args *a) {
   if (!a || a->num_scenes <= 0 || a->scene_rows <= 0) return pcs_set_einval("pcs_head_geometry", "bad geometry");
-  if (pcs_head_stream_class(*a)) {   // the streamed CE head (head_stream.hip): 64-row steps
-    const int64_t tpc = chunk_geo(a->scene_rows, a->num_scenes, 64, &a->chunks_per_scene,
-                                  pcs_head_stream_target());
-    return tpc * 64;
+  if (route::head_stream_class(*a)) {   // the streamed CE head (head_stream.hip): 64-row steps
+    const int64_t tpc = chunk_geo(a->scene_rows, a->num_scenes, route::HS_MS, &a->chunks_per_scene, HS_TARGET);
+    return tpc * route::HS_MS;
   }
   if (a->num_classes <= 4) {   // register-resident kernel: 64-row granules, ~8 WGs per CU
     const int64_t tpc = chunk_geo(a->scene_rows, a->num_scenes, 64, &a->chunks_per_scene, 2048);
@@ -1368,7 +1367,7 @@ extern "C" int pcs_head(const pcs_head_args *ap, pcs_stream_t stream) {
   const int tpc = (int)(rpc / HEAD_R);
   const int nb = (int)(a.num_scenes * a.chunks_per_scene);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (pcs_head_stream_class(a)) return pcs_head_stream_launch(a, rpc, s);
+  if (route::head_stream_class(a)) return pcs_head_stream_launch(a, rpc, s);
   if (a.num_classes <= 4) {
 #define PCS_HS(T, CC, MODE) \
   hipLaunchKernelGGL((head_small_kernel<T, CC, MODE>), dim3(nb), dim3(THREADS), 0, s, a, rpc)

@@ -20,13 +20,11 @@ constexpr int THREADS = 512;
 constexpr int MS = 32;           // rows per step
 constexpr int NB = 256;          // dz5 columns per workgroup
 constexpr int CIN = 128;         // a4 channels
+static_assert(MS == route::WC5_MS && NB == route::WC5_NB && CIN == route::WC5_CIN, "route.h");
 // two stages (66 KB of LDS) so that two workgroups share a CU (512 in the grid): 3.85 -> 3.64 ms
 // in tools/bench_wc5.py against four stages at one workgroup per CU (three: 3.85)
 #ifndef WC5_NST
 #define WC5_NST 2
-#endif
-#ifndef WC5_TARGET
-#define WC5_TARGET 512
 #endif
 constexpr int NST = WC5_NST;     // ring stages
 constexpr int ROWB = NB * 2;     // 512-B dz5 rows in LDS
@@ -203,11 +201,9 @@ __global__ __launch_bounds__(THREADS) void wgrad_c5_kernel(pcs_wgrad_args a, int
 // * both MFMA operands are transposed reads of that tile: wave w accumulates G[16 w + l16][all]
 //   (8 blocks, 32 fp32 per lane); the fp32 column sums ride the transform.
 constexpr int G_MS = 64;                  // rows per step
+static_assert(G_MS == route::GRAM128_MS, "route.h");
 #ifndef GRAM_NST
 #define GRAM_NST 4
-#endif
-#ifndef GRAM_TARGET
-#define GRAM_TARGET 512
 #endif
 constexpr int G_NST = GRAM_NST;
 constexpr int G_YB = G_MS * YROW;         // 16 KB
@@ -375,49 +371,12 @@ __global__ __launch_bounds__(THREADS) void gram128_kernel(pcs_wgrad_args a, int6
 
 }  // namespace
 
-bool pcs_gram128_class(const pcs_wgrad_args &a) {   // shapes / modes only (the split geometry)
-  return a.dtype == PCS_BF16 && !(a.flags & PCS_FLAG_GENERIC) && a.dy_mode == PCS_PRO_BNRELU &&
-         a.x_mode == PCS_PRO_BNRELU && a.Cin == CIN && a.Cout == CIN &&
-         a.num_scenes * a.scene_rows < ((int64_t)1 << 31);
-}
-bool pcs_gram128_applicable(const pcs_wgrad_args &a) {
-  return pcs_gram128_class(a) && a.Y && a.Y == a.X && a.s && a.t && !a.x_mask;
-}
-int pcs_gram128_splits(const pcs_wgrad_args &a) {
-  int64_t sps = (GRAM_TARGET + a.num_scenes - 1) / a.num_scenes;
-  const int64_t max_sps = (a.scene_rows + 4 * G_MS - 1) / (4 * G_MS);   // >= 4 steps per split
-  if (sps > max_sps) sps = max_sps;
-  if (sps < 1) sps = 1;
-  return (int)sps;
-}
 int pcs_gram128_launch(const pcs_wgrad_args &a, hipStream_t s) {
-  int64_t rps = (a.scene_rows + a.splits_per_scene - 1) / a.splits_per_scene;
-  rps = (rps + G_MS - 1) / G_MS * G_MS;
+  const int64_t rps = route::rows_per_split(a.scene_rows, a.splits_per_scene, G_MS);
   const int nb = (int)(a.num_scenes * a.splits_per_scene);
   hipLaunchKernelGGL(gram128_kernel, dim3(nb), dim3(THREADS), 0, s, a, rps);
   PCS_CHECK_LAUNCH();
   return 0;
-}
-
-// conv5's R: bf16, dy_mode RAW (dZ = dz5), x_mode BNRELU without dropout bits, Cin 128,
-// Cout a multiple of 256
-bool pcs_wgrad_c5_class(const pcs_wgrad_args &a) {   // shapes / modes only (the split geometry)
-  return a.dtype == PCS_BF16 && !(a.flags & PCS_FLAG_GENERIC) && a.dy_mode == PCS_PRO_RAW &&
-         a.x_mode == PCS_PRO_BNRELU && a.Cin == CIN && a.Cout % NB == 0 &&
-         a.num_scenes * a.scene_rows < ((int64_t)1 << 31);
-}
-bool pcs_wgrad_c5_applicable(const pcs_wgrad_args &a) {
-  return pcs_wgrad_c5_class(a) && !a.x_mask && a.dZ && a.X && a.s && a.t;
-}
-
-// two 512-thread workgroups per CU: splits per scene so that (Cout / 256) x B x splits ~ 512
-int pcs_wgrad_c5_splits(const pcs_wgrad_args &a) {
-  const int64_t ncb = a.Cout / NB;
-  int64_t sps = (WC5_TARGET + a.num_scenes * ncb - 1) / (a.num_scenes * ncb);
-  const int64_t max_sps = (a.scene_rows + 4 * MS - 1) / (4 * MS);   // >= 4 steps per split
-  if (sps > max_sps) sps = max_sps;
-  if (sps < 1) sps = 1;
-  return (int)sps;
 }
 
 int pcs_wgrad_c5_launch(const pcs_wgrad_args &a, int64_t rows_per_split, hipStream_t s) {
