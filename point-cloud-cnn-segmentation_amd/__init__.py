@@ -35,6 +35,11 @@ _LAZY = {
     "point_lift_mean": ("pointhead", "point_lift_mean"),
     "point_head": ("pointhead", "point_head"),
     "point_head_loss": ("pointhead", "point_head_loss"),
+    "segment_max": ("segmax", "segment_max"),
+    "voxel_max": ("segmax", "voxel_max"),
+    "sparse_max_pool": ("segmax", "sparse_max_pool"),
+    "SparseMaxPool3d": ("segmax", "SparseMaxPool3d"),
+    "point_lift_max": ("segmax", "point_lift_max"),
     "sparse_batch_norm": ("sparse_norm", "sparse_batch_norm"),
     "SparseBatchNorm": ("sparse_norm", "SparseBatchNorm"),
     "SparseResBlock": ("sparse_norm", "SparseResBlock"),

@@ -2,7 +2,8 @@
 
 The header is the table: its structs, prototypes, enumerators and PCS_ABI_VERSION are parsed once
 at import into the ``ct.Structure`` classes, ``SIGNATURES`` and the constants below, so a new entry
-point is declared in the header only (tests/golden/abi_tables.json records the result).
+point is declared in the header only (tests/golden/abi_tables.json records the result).  A header
+of EXT_HEADERS adds entry points of the same library beside pcs.h's (EXT_SIGNATURES).
 
 There is no fallback: if the library is missing or fails to load, every GPU entry point
 raises.  ``torch`` is imported first so that the HIP runtime torch ships (same SONAME
@@ -19,6 +20,9 @@ import torch  # noqa: F401  (loads torch's HIP runtime before libpcs.so)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libpcs.so")
 HEADER_PATH = os.path.join(_HERE, "..", "include", "pcs.h")   # csrc/Makefile's ../../include/pcs.h
+# Headers beside pcs.h that add entry points of the same library and nothing else (no struct, no
+# constant, no change to pcs.h's tables or to PCS_ABI_VERSION): read after pcs.h into EXT_SIGNATURES
+EXT_HEADERS = ("pcs_segmax.h",)
 
 _SCALARS = {"int": ct.c_int, "int32_t": ct.c_int32, "int64_t": ct.c_int64, "uint64_t": ct.c_uint64,
             "float": ct.c_float}
@@ -154,11 +158,30 @@ with open(HEADER_PATH) as _f:
     _consts, _structs, _functions = parse_header(_f.read())
 if "ABI_VERSION" not in _consts:
     _fail("missing define", "PCS_ABI_VERSION")
+
+
+def parse_extension(main_text, ext_text, main=None):
+    """The functions an extension header adds to main_text's (pcs.h's): it is parsed behind pcs.h, which
+    it includes for the types, and may declare functions only.  main: parse_header(main_text), if at
+    hand."""
+    ext_text = re.sub(r'^[ \t]*#include\s+"pcs\.h"[ \t]*$', "", ext_text, flags=re.M)
+    consts, structs, functions = main or parse_header(main_text)
+    c2, s2, f2 = parse_header(main_text + "\n" + ext_text)
+    if c2 != consts or s2 != structs or f2[:len(functions)] != functions:
+        _fail("an extension header may only add functions", ext_text)
+    return f2[len(functions):]
+
+
+_ext_functions = []
+for _h in EXT_HEADERS:
+    with open(HEADER_PATH) as _f, open(os.path.join(os.path.dirname(HEADER_PATH), _h)) as _g:
+        _ext_functions += parse_extension(_f.read(), _g.read(), (_consts, _structs, _functions))
 # F32, BF16, FP8, PRO_*, EPI_*, FLAG_*, HEAD_*, EINVAL, ... and ABI_VERSION (the struct layouts' version)
 globals().update(_consts)
 # GemmArgs, WgradArgs, Seg12Args, Conv3dGeom, PoolBwdArgs, HeadArgs; (name, restype, argtypes) of
 # every function the header declares
-_classes, SIGNATURES, _PARAMS = _bind(_structs, _functions)
+_classes, _signatures, _PARAMS = _bind(_structs, _functions + _ext_functions)
+SIGNATURES, EXT_SIGNATURES = _signatures[:len(_functions)], _signatures[len(_functions):]
 globals().update({c.__name__: c for c in _classes.values()})
 
 _lib = None
@@ -180,7 +203,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or "
             "`make -C point-cloud-cnn-segmentation_amd/csrc`.")
     lib = ct.CDLL(path)
-    for name, res, args in SIGNATURES:
+    for name, res, args in SIGNATURES + EXT_SIGNATURES:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

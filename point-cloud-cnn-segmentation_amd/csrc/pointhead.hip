@@ -5,6 +5,9 @@
 //   lift     Y[v] = inv_count[v] * sum over v's points of relu(W p + b): the Linear + ReLU of a
 //            Cin <= 8 float point is recomputed while the voxel's points are walked; the backward
 //            recomputes the gate z > 0 the same way and reduces dW, db over per-block partials
+//   lift max Y[v] = relu(max over v's points of W p + b), the first maximum in point order (the
+//            statement is tests/segmax_refs.py): the backward re-finds that point per channel and
+//            gives it the whole gradient where its z is positive
 //   project  Z = X W^T, fp32 [V, K]: trilinear interpolation and the head's Linear are both
 //            linear, so the K <= 16 class scores are interpolated instead of the C channels
 //   logits   one thread per point: l = b + sum of the eight corner rows of Z, and (with labels) the
@@ -17,6 +20,7 @@
 // atomically, every output row is stored once, and every sum runs in a fixed order (per-thread
 // ascending, then a fixed block order, then pcs_reduce_partials over at most 2048 non-empty
 // blocks): results are bitwise reproducible.
+#include "../../include/pcs_segmax.h"
 #include "row_piece.h"
 
 namespace {
@@ -159,6 +163,173 @@ __global__ __launch_bounds__(THREADS) void lift_bwd_kernel(const DT *__restrict_
             }
           }
         }
+      }
+    }
+  }
+  // one pass per input column (and one for the bias): a thread per channel sums the row slots
+#pragma unroll
+  for (int q = 0; q <= CIN; ++q) {
+    if (q < CIN || part_b) {   // uniform
+#pragma unroll
+      for (int e = 0; e < E; ++e) sm[e][tid] = q < CIN ? aw[e][q < CIN ? q : 0] : ab[e];
+      __syncthreads();
+      for (int c = tid; c < C; c += THREADS) {
+        const float s = column_sum(sm, c, lpr, rpp);
+        if (q < CIN) part_w[((int64_t)blockIdx.x * C + c) * CIN + q] = s;
+        else part_b[(int64_t)blockIdx.x * C + c] = s;
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// ---- lift, max form: Y[v] = relu(max over v's points of z), the first maximum in point order
+// (common.h's pool_max_step over ascending entries; max relu = relu max)
+// (The mean kernels above keep their loops written out: routed through load_entries or a shared
+// epilogue their device code changes, register allocation at least; tools/asm_equal.py shows it.)
+// SEG_UNROLL entries of a segment from j on: the point ids (-1 past the end j1) and their points
+template <int CIN>
+PCS_DEV void load_entries(const float *__restrict__ P, int64_t ldp, const int32_t *__restrict__ order, int64_t j,
+                          int64_t j1, int32_t (&id)[SEG_UNROLL], float (&p)[SEG_UNROLL][CIN]) {
+#pragma unroll
+  for (int u = 0; u < SEG_UNROLL; ++u) id[u] = j + u < j1 ? order[j + u] : -1;
+#pragma unroll
+  for (int u = 0; u < SEG_UNROLL; ++u) load_point<CIN>(P, ldp, id[u], p[u]);
+}
+
+// the running pick over these entries: pick[e] is the point of channel e's largest z so far,
+// PCS_POOL_NONE until the first present point, which always makes the pick
+template <int CIN>
+PCS_DEV void lift_pick_step(const float (&w)[E][CIN], const float (&b)[E], const int32_t (&id)[SEG_UNROLL],
+                            const float (&p)[SEG_UNROLL][CIN], float (&best)[E], int (&pick)[E]) {
+#pragma unroll
+  for (int u = 0; u < SEG_UNROLL; ++u) {
+    if (id[u] >= 0) {
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const float z = lift_z<CIN>(w[e], b[e], p[u]);
+        const bool wins = pool_max_step(z, best[e], pick[e]);
+        best[e] = wins ? z : best[e];
+        pick[e] = wins ? id[u] : pick[e];
+      }
+    }
+  }
+}
+
+// d[e] * (1, p) of the picked point into the sums
+template <int CIN>
+PCS_DEV void lift_pick_grad(const int (&pick)[E], const float (&d)[E], const int32_t (&id)[SEG_UNROLL],
+                            const float (&p)[SEG_UNROLL][CIN], float (&aw)[E][CIN], float (&ab)[E]) {
+#pragma unroll
+  for (int u = 0; u < SEG_UNROLL; ++u) {
+    if (id[u] >= 0) {
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const float g = pick[e] == id[u] ? d[e] : 0.f;
+        ab[e] += g;
+#pragma unroll
+        for (int i = 0; i < CIN; ++i) aw[e][i] = fmaf(g, p[u][i], aw[e][i]);
+      }
+    }
+  }
+}
+
+template <typename YT, int CIN>
+__global__ __launch_bounds__(THREADS) void lift_max_kernel(const float *__restrict__ P, int64_t ldp,
+                                                           const float *__restrict__ W,
+                                                           const float *__restrict__ bias,
+                                                           const int32_t *__restrict__ order,
+                                                           const int64_t *__restrict__ seg_off, int64_t V, int C,
+                                                           YT *__restrict__ Y) {
+  int rpp, r0, cc;
+  if (!lane_slot(C / E, rpp, r0, cc)) return;
+  const int c0 = cc * E;
+  float w[E][CIN], b[E];
+  load_lift_weights<CIN>(W, bias, c0, w, b);
+  for (int64_t v = (int64_t)blockIdx.x * rpp + r0; v < V; v += (int64_t)gridDim.x * rpp) {
+    const int64_t j0 = seg_off[v], j1 = seg_off[v + 1];
+    float best[E];
+    int seen = PCS_POOL_NONE;   // until the first present point, which always makes the pick
+#pragma unroll
+    for (int e = 0; e < E; ++e) best[e] = 0.f;
+    for (int64_t j = j0; j < j1; j += SEG_UNROLL) {
+      int32_t id[SEG_UNROLL];
+      float p[SEG_UNROLL][CIN];
+      load_entries<CIN>(P, ldp, order, j, j1, id, p);
+#pragma unroll
+      for (int u = 0; u < SEG_UNROLL; ++u) {
+        if (id[u] >= 0) {
+#pragma unroll
+          for (int e = 0; e < E; ++e) {
+            const float z = lift_z<CIN>(w[e], b[e], p[u]);
+            best[e] = pool_max_step(z, best[e], seen) ? z : best[e];
+          }
+          seen = 0;
+        }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) best[e] = relu(best[e]);   // (a voxel without points: relu(0))
+    store_piece<YT, E>(Y + v * C + c0, best);
+  }
+}
+
+// The gradient goes to the one point the forward picked, where its z is positive: a first walk of
+// the segment re-finds the pick per channel, a second one adds dV[v][c] * (1, p_pick) into the sums.
+// The first SEG_UNROLL entries stay in registers between the walks, so a voxel of at most that many
+// points (nearly all of them) loads its points once; a longer one reloads the rest from cache.
+// part_w, part_b as lift_bwd_kernel's.
+template <typename DT, int CIN>
+__global__ __launch_bounds__(THREADS) void lift_max_bwd_kernel(const DT *__restrict__ dV, const float *__restrict__ P,
+                                                               int64_t ldp, const float *__restrict__ W,
+                                                               const float *__restrict__ bias,
+                                                               const int32_t *__restrict__ order,
+                                                               const int64_t *__restrict__ seg_off, int64_t V, int C,
+                                                               int64_t rpb, float *__restrict__ part_w,
+                                                               float *__restrict__ part_b) {
+  __shared__ float sm[E][THREADS];
+  int rpp, r0, cc;
+  const int lpr = C / E, tid = threadIdx.x;
+  const bool active = lane_slot(lpr, rpp, r0, cc);
+  const int64_t lo = (int64_t)blockIdx.x * rpb, hi = pcs_min64(lo + rpb, V);
+  float aw[E][CIN], ab[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    ab[e] = 0.f;
+#pragma unroll
+    for (int i = 0; i < CIN; ++i) aw[e][i] = 0.f;
+  }
+  if (active) {
+    const int c0 = cc * E;
+    float w[E][CIN], b[E];
+    load_lift_weights<CIN>(W, bias, c0, w, b);
+    for (int64_t v = lo + r0; v < hi; v += rpp) {
+      Raw<DT, E> rd;
+      raw_load<DT, E>(rd, dV + v * C + c0, true);
+      const int64_t j0 = seg_off[v], j1 = seg_off[v + 1];
+      float best[E];
+      int pick[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        best[e] = 0.f;
+        pick[e] = PCS_POOL_NONE;
+      }
+      int32_t id0[SEG_UNROLL], id[SEG_UNROLL];
+      float p0[SEG_UNROLL][CIN], p[SEG_UNROLL][CIN];
+      load_entries<CIN>(P, ldp, order, j0, j1, id0, p0);
+      lift_pick_step<CIN>(w, b, id0, p0, best, pick);
+      for (int64_t j = j0 + SEG_UNROLL; j < j1; j += SEG_UNROLL) {
+        load_entries<CIN>(P, ldp, order, j, j1, id, p);
+        lift_pick_step<CIN>(w, b, id, p, best, pick);
+      }
+      float d[E];
+      raw_unpack<DT, E>(rd, d);
+#pragma unroll
+      for (int e = 0; e < E; ++e) pick[e] = best[e] > 0.f ? pick[e] : PCS_POOL_NONE;   // the gate (no point id is NONE)
+      lift_pick_grad<CIN>(pick, d, id0, p0, aw, ab);
+      for (int64_t j = j0 + SEG_UNROLL; j < j1; j += SEG_UNROLL) {
+        load_entries<CIN>(P, ldp, order, j, j1, id, p);
+        lift_pick_grad<CIN>(pick, d, id, p, aw, ab);
       }
     }
   }
@@ -571,6 +742,81 @@ extern "C" int pcs_point_lift_mean_bwd(const void *dV, int32_t dvdtype, const fl
     else                                                                                                            \
       hipLaunchKernelGGL((lift_bwd_kernel<float, CIN>), grid, block, 0, s, static_cast<const float *>(dV), P, ldp, W, \
                          bias, order, seg_off, inv_count, V, (int)C, b.per, part_w, pb);                            \
+  } while (0)
+  PCS_PH_CIN(Cin, PCS_PH_CALL)
+#undef PCS_PH_CALL
+  PCS_CHECK_LAUNCH();
+  const int64_t nw = (int64_t)C * Cin;
+  if (int rc = pcs_reduce_partials(part_w, b.n, nw, 1.f, dW, nw, nw, stream)) return rc;
+  if (db)
+    if (int rc = pcs_reduce_partials(part_b, b.n, C, 1.f, db, C, C, stream)) return rc;
+  return 0;
+}
+
+extern "C" int pcs_point_lift_max(const float *P, int64_t ldp, int32_t Cin, const float *W, const float *bias,
+                                  const int32_t *order, const int64_t *seg_off, int64_t V, int32_t C, void *Y,
+                                  int32_t ydtype, pcs_stream_t stream) {
+  const char *fn = "pcs_point_lift_max";
+  if (V < 0) return pcs_set_einval(fn, "V >= 0 required");
+  if (Cin < 1 || Cin > MAX_CIN) return pcs_set_einval(fn, MSG_CIN);
+  if (ldp < Cin) return pcs_set_einval(fn, "ldp >= Cin required");
+  if (bad_channels(C)) return pcs_set_einval(fn, MSG_C);
+  if (!known(ydtype)) return pcs_set_einval(fn, MSG_DTYPE);
+  if (V == 0) return 0;
+  if (!P || !W || !order || !seg_off || !Y) return pcs_set_einval(fn, "NULL pointer");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid(stream_blocks(V, THREADS / (C / E), 1 << 20)), block(THREADS);
+#define PCS_PH_CALL(CIN)                                                                                              \
+  do {                                                                                                                \
+    if (ydtype == PCS_BF16)                                                                                           \
+      hipLaunchKernelGGL((lift_max_kernel<bf16_t, CIN>), grid, block, 0, s, P, ldp, W, bias, order, seg_off, V,        \
+                         (int)C, static_cast<bf16_t *>(Y));                                                           \
+    else                                                                                                              \
+      hipLaunchKernelGGL((lift_max_kernel<float, CIN>), grid, block, 0, s, P, ldp, W, bias, order, seg_off, V, (int)C, \
+                         static_cast<float *>(Y));                                                                    \
+  } while (0)
+  PCS_PH_CIN(Cin, PCS_PH_CALL)
+#undef PCS_PH_CALL
+  PCS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t pcs_point_lift_max_bwd_workspace(int64_t V, int32_t C, int32_t Cin) {
+  const char *fn = "pcs_point_lift_max_bwd_workspace";
+  if (V < 0) return pcs_set_einval(fn, "V >= 0 required");
+  if (Cin < 1 || Cin > MAX_CIN) return pcs_set_einval(fn, MSG_CIN);
+  if (bad_channels(C)) return pcs_set_einval(fn, MSG_C);
+  return lift_bwd_bytes(V, C, Cin);
+}
+
+extern "C" int pcs_point_lift_max_bwd(const void *dV, int32_t dvdtype, const float *P, int64_t ldp, int32_t Cin,
+                                      const float *W, const float *bias, const int32_t *order, const int64_t *seg_off,
+                                      int64_t V, int32_t C, void *workspace, int64_t workspace_bytes, float *dW,
+                                      float *db, pcs_stream_t stream) {
+  const char *fn = "pcs_point_lift_max_bwd";
+  if (V < 0) return pcs_set_einval(fn, "V >= 0 required");
+  if (Cin < 1 || Cin > MAX_CIN) return pcs_set_einval(fn, MSG_CIN);
+  if (ldp < Cin) return pcs_set_einval(fn, "ldp >= Cin required");
+  if (bad_channels(C)) return pcs_set_einval(fn, MSG_C);
+  if (!known(dvdtype)) return pcs_set_einval(fn, MSG_DTYPE);
+  if (V == 0) return 0;
+  if (!dV || !P || !W || !order || !seg_off || !dW) return pcs_set_einval(fn, "NULL pointer");
+  if (!workspace || misaligned(workspace) || workspace_bytes < lift_bwd_bytes(V, C, Cin))
+    return pcs_set_einval(fn, MSG_WS);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const Blocks b = reduction_blocks(V, ROW_TILE);
+  float *part_w = static_cast<float *>(workspace);
+  float *part_b = part_w + (int64_t)b.n * C * Cin;
+  float *pb = db ? part_b : nullptr;
+  const dim3 grid(b.n), block(THREADS);
+#define PCS_PH_CALL(CIN)                                                                                             \
+  do {                                                                                                               \
+    if (dvdtype == PCS_BF16)                                                                                         \
+      hipLaunchKernelGGL((lift_max_bwd_kernel<bf16_t, CIN>), grid, block, 0, s, static_cast<const bf16_t *>(dV), P,   \
+                         ldp, W, bias, order, seg_off, V, (int)C, b.per, part_w, pb);                                \
+    else                                                                                                             \
+      hipLaunchKernelGGL((lift_max_bwd_kernel<float, CIN>), grid, block, 0, s, static_cast<const float *>(dV), P, ldp, \
+                         W, bias, order, seg_off, V, (int)C, b.per, part_w, pb);                                     \
   } while (0)
   PCS_PH_CIN(Cin, PCS_PH_CALL)
 #undef PCS_PH_CALL

@@ -398,6 +398,15 @@ class CoarseLink:
     coarse: int
     _down: tuple = field(default=None, repr=False)
     _up: tuple = field(default=None, repr=False)
+    _cells: tuple = field(default=None, repr=False)
+
+    def child_segments(self):
+        """(src int32 [8 Vc], seg_off int64 [Vc + 1]): the child map as segments of eight taps, one per
+        coarse voxel in tap order (segmax.sparse_max_pool's), built once."""
+        if self._cells is None:
+            seg_off = torch.arange(self.coarse + 1, dtype=torch.int64, device=self.child.device) * K2_TAPS
+            self._cells = (self.child.reshape(-1), seg_off)
+        return self._cells
 
     def down_pairs(self):
         """Pair lists of the child map (in: fine row, out: coarse row), as SparseVoxels.pairs()."""

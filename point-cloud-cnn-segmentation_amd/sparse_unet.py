@@ -25,6 +25,7 @@ import torch
 from .data import RaggedBatch
 from .pointhead import point_head, point_head_loss, point_lift_mean
 from .pointvoxel import devoxelize, point_voxel_map, voxel_mean
+from .segmax import point_lift_max, voxel_max
 from .sparse import (CoarseLink, SparseDownConv3d, SparseUpConv3d, SparseVoxels, SubMConv3dCat, coarsen,
                      sparse_voxels)
 from .sparse_norm import SparseBatchNorm, SparseResBlock
@@ -105,11 +106,16 @@ class SparseUNetSegmentation(torch.nn.Module):
     sparse_voxels -> sparse_pyramid -> point_voxel_map -> relu(Linear(in_channels, w_0)) on the points
     -> voxel_mean -> SparseUNet -> trilinear devoxelize -> Linear(w_0, num_classes).  Returns fp32
     logits [T, num_classes] in the batch's point order (the first in_channels columns of the points
-    feed the lift).  grid must be divisible by 2**(len(widths) - 1)."""
+    feed the lift).  grid must be divisible by 2**(len(widths) - 1).  lift="max" takes voxel_max in
+    voxel_mean's place (the PointNet-style voxel feature encoder; segmax.point_lift_max on the fused
+    path) with the same parameters and state_dict."""
 
     def __init__(self, in_channels=4, num_classes=2, widths=(64, 128, 256), grid=64, lo=(-1.0, -1.0, -1.0),
-                 hi=(1.0, 1.0, 1.0)):
+                 hi=(1.0, 1.0, 1.0), lift="mean"):
         super().__init__()
+        if lift not in ("mean", "max"):
+            raise ValueError(f"SparseUNetSegmentation: lift must be 'mean' or 'max', got {lift!r}")
+        self.lift_mode = lift
         self.unet = SparseUNet(widths)
         if grid <= 0 or grid % (1 << self.unet.depth) != 0:
             raise ValueError(f"SparseUNetSegmentation: grid {grid} is not divisible by 2**{self.unet.depth}")
@@ -132,8 +138,9 @@ class SparseUNetSegmentation(torch.nn.Module):
         return dev, pyr, point_voxel_map(rb, sv, self.lo, self.hi)
 
     def _fused_features(self, rb, dev, pyr, pvm):
-        """The U-Net's output on the finest level with the lift fused into the voxel mean."""
-        x = point_lift_mean(rb.points.to(dev, torch.float32), self.lift.weight, self.lift.bias, pvm)
+        """The U-Net's output on the finest level with the lift fused into the voxel mean (lift="max": the voxel max)."""
+        fn = point_lift_max if self.lift_mode == "max" else point_lift_mean
+        x = fn(rb.points.to(dev, torch.float32), self.lift.weight, self.lift.bias, pvm)
         return self.unet(x, pyr)
 
     def forward(self, rb: RaggedBatch, fused: bool = False):
@@ -143,7 +150,7 @@ class SparseUNetSegmentation(torch.nn.Module):
         if fused:
             return point_head(self._fused_features(rb, dev, pyr, pvm), pvm, self.head.weight, self.head.bias)
         pts = rb.points.to(dev, torch.float32)[:, :self.in_channels]
-        x = voxel_mean(torch.relu(self.lift(pts)), pvm)
+        x = (voxel_max if self.lift_mode == "max" else voxel_mean)(torch.relu(self.lift(pts)), pvm)
         x = self.unet(x, pyr)
         return self.head(devoxelize(x, pvm))
 
