@@ -49,6 +49,13 @@ _LAZY = {
     "sparse_pyramid": ("sparse_unet", "sparse_pyramid"),
     "SparseUNet": ("sparse_unet", "SparseUNet"),
     "SparseUNetSegmentation": ("sparse_unet", "SparseUNetSegmentation"),
+    "conv3d_cat": ("voxel", "conv3d_cat"),
+    "Conv3dCat": ("voxel", "Conv3dCat"),
+    "dense_point_map": ("voxel_unet", "dense_point_map"),
+    "VoxelBatchNorm": ("voxel_unet", "VoxelBatchNorm"),
+    "VoxelResBlock": ("voxel_unet", "VoxelResBlock"),
+    "VoxelUNet": ("voxel_unet", "VoxelUNet"),
+    "VoxelUNetSegmentation": ("voxel_unet", "VoxelUNetSegmentation"),
 }
 
 

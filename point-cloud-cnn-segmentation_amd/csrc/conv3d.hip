@@ -28,6 +28,7 @@
 // their output likewise (Out1 / Out2): the two-source layer pcs_sparse_conv_cat*, a decoder's
 // convolution of [up | skip] without the concatenated array, in the same k-step order.
 // The 3x3x3 stride-1 stencil has its own halo-staged kernels (stencil3_kernel, stencil3_wgrad_kernel).
+#include "../../include/pcs_dense.h"
 #include "kernel_prims.h"
 
 namespace {
@@ -43,9 +44,11 @@ PCS_DEV int cswz(int row, int slot) { return slot ^ ((-(row >> 2)) & 3); }
 // [rows, CA] | [rows, Cin - CA] read as their concatenation along channels (Rows2: a U-Net decoder's
 // [up, skip] without the copy).  Arg is what a kernel takes (a plain pointer for one array, so the
 // single-source kernels keep their arguments) and at(X, row, Cin, c) the address of channel c of a
-// row.  c and CA are multiples of 64, the widest channel slice a k-step or a weight-gradient tile
-// reads, so a slice never straddles the blocks and the choice is uniform over the workgroup; the
-// order of k-steps is that of the concatenated array, so the sums are bit-identical to it.
+// row.  In the sparse kernels c and CA are multiples of 64, the widest channel slice a k-step or a
+// weight-gradient tile reads, so a slice never straddles the blocks and the choice is uniform over
+// the workgroup; the dense stencil kernels call at() per 16-byte chunk (c a multiple of 8, CA of 32),
+// so a 64-channel slice may straddle the blocks.  Either way the order of k-steps is that of the
+// concatenated array, so the sums are bit-identical to it.
 struct Rows1 {
   static constexpr bool SPLIT = false;
   using Arg = const bf16_t *__restrict__;
@@ -61,8 +64,9 @@ struct Rows2 {
   }
 };
 // The same for an output Y [rows, Cout]: pick(Y, c0, ld) takes the first channel c0 of a 64-channel
-// tile (or 8-channel chunk) and ld = Cout, returns the array that holds it and turns (c0, ld) into
-// the channel and the leading dimension there (Out2: an input gradient written as two column blocks).
+// tile (or 8-channel chunk; the dense stencil: of a 4-channel store group, so a tile may straddle
+// the blocks) and ld = Cout, returns the array that holds it and turns (c0, ld) into the channel and
+// the leading dimension there (Out2: an input gradient written as two column blocks).
 struct Out1 {
   static constexpr bool SPLIT = false;
   using Arg = void *__restrict__;
@@ -359,7 +363,9 @@ __global__ __launch_bounds__(THREADS) void conv3d_kernel(pcs_conv3d_geom g, cons
 // reads its 6 x 6 x 10 input halo (360 voxel rows) from L2 once and every tap's A operand from
 // LDS at a shifted row, instead of 27 gathers; the 27 taps' NT x CS weight tiles (NT = 64 or 32
 // output channels) stream through a double buffer.  The LDS images keep 128-B rows whatever CS
-// (a 32-channel slice fills the first four swizzled slots of a row).
+// (a 32-channel slice fills the first four swizzled slots of a row).  X: Rows1, or Rows2 (the
+// two-source forward pcs_conv3d_cat: the halo staging picks the source per 16-byte chunk); Y: Out1,
+// or Out2 (its input gradient, the transposed form writing dXA | dXB per 4-channel store group).
 constexpr int SZ = 4, SY = 4, SX = 8;                      // output block: 128 voxels
 constexpr int GZ = SZ + 2, GY = SY + 2, GX = SX + 2;
 constexpr int HROWS = GZ * GY * GX;                        // 360 halo voxels
@@ -367,10 +373,10 @@ constexpr int HIMG = HROWS * 128, WTILE = 64 * 128;        // halo image (64 ch)
 
 PCS_DEV int swz8(int row, int ch) { return ch ^ ((row >> 1) & 7); }
 
-template <int CS, int NT, bool OUT_BF16>
-__global__ __launch_bounds__(THREADS) void stencil3_kernel(pcs_conv3d_geom g, const bf16_t *__restrict__ X,
+template <int CS, int NT, bool OUT_BF16, class XF = Rows1, class YF = Out1>
+__global__ __launch_bounds__(THREADS) void stencil3_kernel(pcs_conv3d_geom g, typename XF::Arg X,
                                                            const bf16_t *__restrict__ W, const float *__restrict__ bias,
-                                                           void *__restrict__ Y) {
+                                                           typename YF::Arg Y) {
   __shared__ __attribute__((aligned(16))) char lds[HIMG + 2 * WTILE];   // 45 KB + 16 KB
   char *halo = lds, *wt = lds + HIMG;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -427,7 +433,7 @@ __global__ __launch_bounds__(THREADS) void stencil3_kernel(pcs_conv3d_geom g, co
       const int iz = hz0 + hz, iy = hy0 + hy, ix = hx0 + hx;
       u32x4 v = mk_u32x4(0, 0, 0, 0);
       if (iz >= 0 && iy >= 0 && ix >= 0 && iz < g.Di && iy < g.Hi && ix < g.Wi)
-        v = *reinterpret_cast<const u32x4 *>(X + ((((int64_t)b * g.Di + iz) * g.Hi + iy) * g.Wi + ix) * Cin + c0 + ch * 8);
+        v = *reinterpret_cast<const u32x4 *>(XF::at(X, (((int64_t)b * g.Di + iz) * g.Hi + iy) * g.Wi + ix, Cin, c0 + ch * 8));
       *reinterpret_cast<u32x4 *>(halo + hr * 128 + swz8(hr, ch) * 16) = v;
     }
     loadw(0, c0);
@@ -474,11 +480,13 @@ __global__ __launch_bounds__(THREADS) void stencil3_kernel(pcs_conv3d_geom g, co
         const float4 bb = *reinterpret_cast<const float4 *>(bias + co);
         v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
       }
+      int cy = co, ld = g.Cout;
+      void *y = YF::pick(Y, cy, ld);
       if constexpr (OUT_BF16) {
-        *reinterpret_cast<uint2 *>(reinterpret_cast<bf16_t *>(Y) + uo * g.Cout + co) =
+        *reinterpret_cast<uint2 *>(reinterpret_cast<bf16_t *>(y) + uo * ld + cy) =
             make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
       } else {
-        *reinterpret_cast<float4 *>(reinterpret_cast<float *>(Y) + uo * g.Cout + co) = make_float4(v[0], v[1], v[2], v[3]);
+        *reinterpret_cast<float4 *>(reinterpret_cast<float *>(y) + uo * ld + cy) = make_float4(v[0], v[1], v[2], v[3]);
       }
     }
   }
@@ -659,11 +667,11 @@ __global__ __launch_bounds__(THREADS) void conv3d_wgrad_kernel(pcs_conv3d_geom g
 // one (64 co x 64 ci) tile and one dz (9 taps, 144 accumulator VGPRs) and walks a range of 4 x 4 x 8
 // output blocks; per block it stages the block's dY rows [128][64] and the 4 input planes of the
 // halo it meets at this dz [4][6][10][64] once, and every tap's operand is a shifted set of halo
-// rows read transposed (k over the block's voxels)
+// rows read transposed (k over the block's voxels).  X: Rows1 or Rows2 (per 16-byte chunk, as above)
 constexpr int XPL = SZ * GY * GX;   // 240 halo rows of one dz
 
-template <int COT, int CIT>   // the (co, ci) tile: 64 or 32 each
-__global__ __launch_bounds__(THREADS) void stencil3_wgrad_kernel(pcs_conv3d_geom g, const bf16_t *__restrict__ X,
+template <int COT, int CIT, class XF = Rows1>   // the (co, ci) tile: 64 or 32 each
+__global__ __launch_bounds__(THREADS) void stencil3_wgrad_kernel(pcs_conv3d_geom g, typename XF::Arg X,
                                                                  const bf16_t *__restrict__ dY, float *__restrict__ ws,
                                                                  int64_t nblk, int64_t bps) {
   __shared__ __attribute__((aligned(16))) char lds[(128 + XPL) * 128];   // dY image | halo planes (46 KB)
@@ -725,7 +733,7 @@ __global__ __launch_bounds__(THREADS) void stencil3_wgrad_kernel(pcs_conv3d_geom
       const int iz = hz0 + hz, iy = hy0 + hy, ix = hx0 + hx;
       u32x4 v = mk_u32x4(0, 0, 0, 0);
       if (iz >= 0 && iy >= 0 && ix >= 0 && iz < g.Di && iy < g.Hi && ix < g.Wi)
-        v = *reinterpret_cast<const u32x4 *>(X + ((((int64_t)b * g.Di + iz) * g.Hi + iy) * g.Wi + ix) * g.Cin + ci0 + ch * 8);
+        v = *reinterpret_cast<const u32x4 *>(XF::at(X, (((int64_t)b * g.Di + iz) * g.Hi + iy) * g.Wi + ix, g.Cin, ci0 + ch * 8));
       *reinterpret_cast<u32x4 *>(ximg + hr * 128 + ((ch ^ ((hr >> 1) & 7)) << 4)) = v;
     }
     __syncthreads();
@@ -1326,6 +1334,43 @@ int launch_sparse_wgrad(const char *who, const int32_t *nbr, int64_t M, int taps
   return db ? bias_grad(dY, Cout, M, sp, vps, wsb, db, s, who) : 0;
 }
 
+// The launches behind the dense stencil entry points (g: a stencil3 geometry, checked): XF is Rows1
+// or Rows2, YF Out1 or Out2; the tiles are ctile(g.Cin) x ctile(g.Cout) whatever the source, so the
+// two-source layer runs the split geometry of the layer on the concatenated array.
+
+// stencil3_kernel over the 4 x 4 x 8 output blocks
+template <class XF, class YF>
+int launch_stencil3(const char *who, const pcs_conv3d_geom &g, typename XF::Arg X, const void *W, const float *bias,
+                    typename YF::Arg Y, int ydtype, hipStream_t s) {
+  const int cs = ctile(g.Cin), nt = ctile(g.Cout);
+  const int64_t nblk = stencil_blocks(g);
+  if (nblk > 0x7fffffff) return pcs_set_einval(who, "grid too large");
+  const dim3 sg((unsigned)nblk, (unsigned)(g.Cout / nt));
+  const bf16_t *Ws = static_cast<const bf16_t *>(W);
+#define PCS_S3(CS, NT)                                                                                          \
+  do {                                                                                                          \
+    if (ydtype == PCS_BF16) hipLaunchKernelGGL((stencil3_kernel<CS, NT, true, XF, YF>), sg, dim3(THREADS), 0, s, g, X, Ws, bias, Y); \
+    else hipLaunchKernelGGL((stencil3_kernel<CS, NT, false, XF, YF>), sg, dim3(THREADS), 0, s, g, X, Ws, bias, Y);   \
+  } while (0)
+  if (cs == 64) { if (nt == 64) PCS_S3(64, 64); else PCS_S3(64, 32); }
+  else { if (nt == 64) PCS_S3(32, 64); else PCS_S3(32, 32); }
+#undef PCS_S3
+  return launched(who);
+}
+
+// stencil3_wgrad_kernel's sp block-range partials into ws (the caller checks the launch and sums them)
+template <class XF>
+void launch_stencil3_wgrad(const pcs_conv3d_geom &g, typename XF::Arg X, const bf16_t *dY, float *ws, int64_t sp,
+                           hipStream_t s) {
+  const int cot = ctile(g.Cout), cit = ctile(g.Cin);
+  const int64_t nb = stencil_blocks(g), bps = (nb + sp - 1) / sp;
+  const dim3 grid((unsigned)((g.Cout / cot) * (g.Cin / cit)), 3u, (unsigned)sp);
+#define PCS_SW(CO, CI) hipLaunchKernelGGL((stencil3_wgrad_kernel<CO, CI, XF>), grid, dim3(THREADS), 0, s, g, X, dY, ws, nb, bps)
+  if (cot == 64) { if (cit == 64) PCS_SW(64, 64); else PCS_SW(64, 32); }
+  else { if (cit == 64) PCS_SW(32, 64); else PCS_SW(32, 32); }
+#undef PCS_SW
+}
+
 }  // namespace
 
 extern "C" int pcs_conv3d(const pcs_conv3d_geom *g, const void *X, const void *W, const float *bias, void *Y,
@@ -1339,22 +1384,8 @@ extern "C" int pcs_conv3d(const pcs_conv3d_geom *g, const void *X, const void *W
   const int64_t M = out_voxels(*g);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int cs = ctile(g->Cin), nt = ctile(g->Cout);
-  if (stencil3(*g)) {   // halo-staged stencil (both forms)
-    const int64_t nblk = stencil_blocks(*g);
-    if (nblk > 0x7fffffff) return pcs_set_einval("pcs_conv3d", "grid too large");
-    const dim3 sg((unsigned)nblk, (unsigned)(g->Cout / nt));
-    const bf16_t *Xs = static_cast<const bf16_t *>(X), *Ws = static_cast<const bf16_t *>(W);
-#define PCS_S3(CS, NT)                                                                                          \
-  do {                                                                                                          \
-    if (ydtype == PCS_BF16) hipLaunchKernelGGL((stencil3_kernel<CS, NT, true>), sg, dim3(THREADS), 0, s, *g, Xs, Ws, bias, Y); \
-    else hipLaunchKernelGGL((stencil3_kernel<CS, NT, false>), sg, dim3(THREADS), 0, s, *g, Xs, Ws, bias, Y);   \
-  } while (0)
-    if (cs == 64) { if (nt == 64) PCS_S3(64, 64); else PCS_S3(64, 32); }
-    else { if (nt == 64) PCS_S3(32, 64); else PCS_S3(32, 32); }
-#undef PCS_S3
-    PCS_CHECK_LAUNCH();
-    return 0;
-  }
+  if (stencil3(*g))   // halo-staged stencil (both forms)
+    return launch_stencil3<Rows1, Out1>("pcs_conv3d", *g, static_cast<const bf16_t *>(X), W, bias, Y, ydtype, s);
   // transposed stride 2: 8 parity classes, tiles of the largest class's sub-grid each.  128-voxel
   // tiles (8 MFMAs per wave per barrier) once there are enough of them to fill the chip
   const int64_t rows_cls = g->transposed && g->s == 2 ? g->B * ((g->Do + 1) / 2) * ((g->Ho + 1) / 2) * ((g->Wo + 1) / 2) : M;
@@ -1402,12 +1433,7 @@ extern "C" int pcs_conv3d_wgrad(const pcs_conv3d_geom *g, const void *X, const v
   const unsigned ntile = (unsigned)((g->Cout / cot) * (g->Cin / cit));
   const bf16_t *Xb = static_cast<const bf16_t *>(X), *dYb = static_cast<const bf16_t *>(dY);
   if (stencil3(*g)) {
-    const int64_t nb = stencil_blocks(*g), bps = (nb + sp - 1) / sp;
-    const dim3 grid(ntile, 3u, (unsigned)sp);
-#define PCS_SW(CO, CI) hipLaunchKernelGGL((stencil3_wgrad_kernel<CO, CI>), grid, dim3(THREADS), 0, s, *g, Xb, dYb, ws, nb, bps)
-    if (cot == 64) { if (cit == 64) PCS_SW(64, 64); else PCS_SW(64, 32); }
-    else { if (cit == 64) PCS_SW(32, 64); else PCS_SW(32, 32); }
-#undef PCS_SW
+    launch_stencil3_wgrad<Rows1>(*g, Xb, dYb, ws, sp, s);
   } else {
     const int groups = g->transposed && g->s == 2 ? taps : g->k * g->k;   // workgroups per (co, ci) tile and slice
     const dim3 grid(ntile, (unsigned)groups, (unsigned)sp);
@@ -1727,4 +1753,58 @@ extern "C" int pcs_sparse_conv_cat_wgrad_pairs(const int32_t *pair_in, const int
   pair_wgrad_slices(&pt, CA + CB, Cout);
   return launch_pair_wgrad<Rows2>(__func__, pt, pair_in, pair_out, M, rows2(XA, CA, XB), CA + CB, dY, Cout, workspace, dW, db,
                            reinterpret_cast<hipStream_t>(stream));
+}
+
+// ---- the two-source dense stencil (include/pcs_dense.h): stencil3_kernel / stencil3_wgrad_kernel on
+// X = [XA | XB] along channels (Rows2), the input gradient written as dXA | dXB (Out2).  The tiles,
+// the k-step order, the block ranges and the workspace are those of pcs_conv3d / pcs_conv3d_wgrad at
+// Cin = CA + CB, so every result is bit-identical to the layer on the concatenated array.
+namespace {
+// the rules the three entry points share, or nullptr; cat = the geometry's channel count that is split
+// into CA | CB, other = the one that is not
+const char *dense_cat_bad(const pcs_conv3d_geom *g, int cat, int other, int CA, int CB, int dtype) {
+  const char *why = nullptr;
+  if (!geom_ok(g, &why)) return why;
+  if (!stencil3(*g)) return "the two-source layer is the 3x3x3 stride-1 stencil (k == 3, s == 1)";
+  if (CA <= 0 || CB <= 0 || other <= 0 || CA % 32 != 0 || CB % 32 != 0 || other % 32 != 0 || CA > (1 << 20) ||
+      CB > (1 << 20))
+    return "CA, CB and Cout must be positive multiples of 32";
+  if (cat != CA + CB) return "the geometry's channel count must be CA + CB";
+  if (dtype != PCS_F32 && dtype != PCS_BF16) return "output dtype: PCS_F32 or PCS_BF16";
+  if (stencil_blocks(*g) > 0x7fffffff) return "grid too large";
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int pcs_conv3d_cat(const pcs_conv3d_geom *g, const void *XA, int32_t CA, const void *XB, int32_t CB,
+                              const void *W, const float *bias, void *Y, int32_t ydtype, pcs_stream_t stream) {
+  if (const char *why = dense_cat_bad(g, g ? g->Cin : 0, g ? g->Cout : 0, CA, CB, ydtype)) return pcs_set_einval(__func__, why);
+  if (!XA || !XB || !W || !Y) return pcs_set_einval(__func__, "NULL XA, XB, W or Y");
+  return launch_stencil3<Rows2, Out1>(__func__, *g, rows2(XA, CA, XB), W, bias, Y, ydtype, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int pcs_conv3d_cat_dgrad(const pcs_conv3d_geom *g, const void *dY, const void *Wt, void *dXA, int32_t CA,
+                                    void *dXB, int32_t CB, int32_t xdtype, pcs_stream_t stream) {
+  if (const char *why = dense_cat_bad(g, g ? g->Cout : 0, g ? g->Cin : 0, CA, CB, xdtype)) return pcs_set_einval(__func__, why);
+  if (!dY || !Wt || !dXA || !dXB) return pcs_set_einval(__func__, "NULL dY, Wt, dXA or dXB");
+  return launch_stencil3<Rows1, Out2>(__func__, *g, static_cast<const bf16_t *>(dY), Wt, nullptr, Out2{dXA, dXB, CA}, xdtype,
+                                      reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int pcs_conv3d_cat_wgrad(const pcs_conv3d_geom *g, const void *XA, int32_t CA, const void *XB, int32_t CB,
+                                    const void *dY, void *workspace, int64_t workspace_bytes, float *dW, float *db,
+                                    pcs_stream_t stream) {
+  if (const char *why = dense_cat_bad(g, g ? g->Cin : 0, g ? g->Cout : 0, CA, CB, PCS_BF16)) return pcs_set_einval(__func__, why);
+  if (!XA || !XB || !dY || !dW || !workspace) return pcs_set_einval(__func__, "NULL XA, XB, dY, dW or workspace");
+  if (workspace_bytes < pcs_conv3d_wgrad_workspace(g))
+    return pcs_set_einval(__func__, "the workspace is shorter than pcs_conv3d_wgrad_workspace(g) at Cin = CA + CB");
+  const int64_t M = out_voxels(*g), sp = wgrad_splits(*g), vps = wgrad_vps(*g, sp);
+  const int64_t wlen = (int64_t)g->Cout * 27 * g->Cin;
+  float *ws = static_cast<float *>(workspace), *wsb = ws + sp * wlen;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  launch_stencil3_wgrad<Rows2>(*g, rows2(XA, CA, XB), static_cast<const bf16_t *>(dY), ws, sp, s);
+  if (const int rc = launched(__func__)) return rc;
+  hipLaunchKernelGGL(conv3d_reduce_kernel, dim3((unsigned)((wlen + 255) / 256)), dim3(256), 0, s, ws, sp, wlen, dW);
+  if (const int rc = launched(__func__)) return rc;
+  return db ? bias_grad(dY, g->Cout, M, sp, vps, wsb, db, s, __func__) : 0;
 }

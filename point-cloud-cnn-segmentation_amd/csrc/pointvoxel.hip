@@ -15,6 +15,7 @@
 // flight before it accumulates in fp32.  Each output row is stored once (a zero row when nothing
 // contributes), nothing is added atomically, and every sum runs in a fixed order: results are
 // bitwise reproducible.
+#include "../../include/pcs_dense.h"
 #include "row_piece.h"
 #include "voxel_geom.h"
 #include "voxel_hash.h"
@@ -28,11 +29,25 @@ using pcs_hash::hash_find;
 constexpr int MAX_K = 8;
 constexpr int SEG_UNROLL = 4;   // row loads a lane keeps in flight along a segment
 
-// one thread per point
+// Where the voxels of a level are: row(key) is the row of the voxel with key scene * G^3 + (ix * G +
+// iy) * G + iz, or -1 when the level does not hold it.  An occupied-voxel level looks the key up in
+// its hash table; a dense grid holds every cell at the row that is its key (below 2^31, checked by
+// pcs_dense_trilinear_index), so it needs no table.
+struct HashLevel {
+  const uint64_t *tk;
+  const int32_t *tv;
+  uint64_t mask;
+  PCS_DEV int32_t row(uint64_t key) const { return hash_find(tk, tv, mask, key); }
+};
+struct DenseLevel {
+  PCS_DEV int32_t row(uint64_t key) const { return (int32_t)key; }
+};
+
+// one thread per point; Level is HashLevel or DenseLevel: one set of float32 expressions for both
+template <class Level>
 __global__ __launch_bounds__(THREADS) void trilinear_index_kernel(
     const float *__restrict__ pts, const int64_t *__restrict__ offsets, int B, int64_t T, int G, Box bx,
-    const uint64_t *__restrict__ tk, const int32_t *__restrict__ tv, uint64_t mask, int32_t *__restrict__ own,
-    int32_t *__restrict__ corner, float *__restrict__ weight) {
+    Level lv, int32_t *__restrict__ own, int32_t *__restrict__ corner, float *__restrict__ weight) {
   const uint64_t G3 = (uint64_t)G * G * G;
   for (int64_t t = (int64_t)blockIdx.x * THREADS + threadIdx.x; t < T; t += (int64_t)gridDim.x * THREADS) {
     int lo = 0, hi = B;   // scene: last b with offsets[b] <= t
@@ -57,7 +72,7 @@ __global__ __launch_bounds__(THREADS) void trilinear_index_kernel(
       bv[d] = (int)b;
       fv[d] = __fsub_rn(c, b);
     }
-    own[t] = hash_find(tk, tv, mask, base + ((uint64_t)iv[0] * G + iv[1]) * G + iv[2]);
+    own[t] = lv.row(base + ((uint64_t)iv[0] * G + iv[1]) * G + iv[2]);
     int32_t row[MAX_K];
     float raw[MAX_K], sum = 0.f;
 #pragma unroll
@@ -66,7 +81,7 @@ __global__ __launch_bounds__(THREADS) void trilinear_index_kernel(
       const int jx = bv[0] + ax, jy = bv[1] + ay, jz = bv[2] + az;
       int32_t r = -1;
       if (jx >= 0 && jx < G && jy >= 0 && jy < G && jz >= 0 && jz < G)
-        r = hash_find(tk, tv, mask, base + ((uint64_t)jx * G + jy) * G + jz);
+        r = lv.row(base + ((uint64_t)jx * G + jy) * G + jz);
       const float wk = (ax ? fv[0] : 1.f - fv[0]) * (ay ? fv[1] : 1.f - fv[1]) * (az ? fv[2] : 1.f - fv[2]);
       row[k] = r;
       raw[k] = r >= 0 ? wk : 0.f;
@@ -204,9 +219,28 @@ extern "C" int pcs_trilinear_index(const float *points, const int64_t *offsets, 
     return pcs_set_einval("pcs_trilinear_index", "NULL pointer");
   if (T == 0) return 0;
   const Box b = {{lo_x, lo_y, lo_z}, {hi_x, hi_y, hi_z}};
-  hipLaunchKernelGGL(trilinear_index_kernel, dim3(pcs_geom::blocks_1d(T)), dim3(THREADS), 0,
+  hipLaunchKernelGGL(trilinear_index_kernel<HashLevel>, dim3(pcs_geom::blocks_1d(T)), dim3(THREADS), 0,
                      reinterpret_cast<hipStream_t>(stream), points, offsets, (int)num_scenes, T, (int)grid, b,
-                     table_keys, table_vals, (uint64_t)(capacity - 1), own, corner, weight);
+                     HashLevel{table_keys, table_vals, (uint64_t)(capacity - 1)}, own, corner, weight);
+  PCS_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int pcs_dense_trilinear_index(const float *points, const int64_t *offsets, int64_t num_scenes, int64_t T,
+                                         int32_t grid, float lo_x, float lo_y, float lo_z, float hi_x, float hi_y,
+                                         float hi_z, int32_t *own, int32_t *corner, float *weight,
+                                         pcs_stream_t stream) {
+  if (T < 0 || num_scenes < 1) return pcs_set_einval(__func__, "T >= 0 and num_scenes >= 1 required");
+  if (grid < 1 || grid > (1 << 20)) return pcs_set_einval(__func__, "1 <= grid <= 2^20 required");
+  if (!(hi_x > lo_x && hi_y > lo_y && hi_z > lo_z)) return pcs_set_einval(__func__, "hi > lo required");
+  if ((double)grid * grid * grid * (double)num_scenes >= 2147483648.0)
+    return pcs_set_einval(__func__, "row overflow (num_scenes * grid^3 >= 2^31)");
+  if (!offsets || (T > 0 && (!points || !own || !corner || !weight))) return pcs_set_einval(__func__, "NULL pointer");
+  if (T == 0) return 0;
+  const Box b = {{lo_x, lo_y, lo_z}, {hi_x, hi_y, hi_z}};
+  hipLaunchKernelGGL(trilinear_index_kernel<DenseLevel>, dim3(pcs_geom::blocks_1d(T)), dim3(THREADS), 0,
+                     reinterpret_cast<hipStream_t>(stream), points, offsets, (int)num_scenes, T, (int)grid, b,
+                     DenseLevel{}, own, corner, weight);
   PCS_CHECK_LAUNCH();
   return 0;
 }

@@ -287,3 +287,103 @@ class ConvTranspose3d(torch.nn.Module):
 
     def forward(self, x, out_dtype=torch.bfloat16):
         return conv_transpose3d(x, self.weight, self.bias, self.stride, self.padding, out_dtype, self.output_padding)
+
+
+# ---- the two-source stencil (pcs_conv3d_cat*, include/pcs_dense.h): a decoder's convolution of
+# (up, skip) without the concatenated grid
+class _Conv3dCatFn(torch.autograd.Function):
+    """_Conv3dFn (k = 3, s = 1, p = 1) on x = [xa | xb] along channels (ca, cb and cout multiples of
+    32), which is never built: the kernels read the two grids, autograd keeps xa and xb themselves,
+    and one stencil pass over dy writes both input gradients.  Tiles, k-step order and workspace are
+    _Conv3dFn's at ca + cb input channels."""
+
+    @staticmethod
+    def forward(ctx, xa, xb, wk, bias, out_dtype):
+        B, D, H, W, ca = xa.shape
+        cb, cout = xb.shape[-1], wk.shape[0]
+        xa, xb = xa.contiguous(), xb.contiguous()
+        wb = _bf16_2d(wk, cout, 27 * (ca + cb))
+        bk = None if bias is None else bias.float().contiguous()
+        g = _geom(B, (D, H, W), ca + cb, cout, 3, 1, 1, False)
+        y = torch.empty(B, D, H, W, cout, dtype=out_dtype, device=xa.device)
+        L.call("pcs_conv3d_cat", g, xa, ca, xb, cb, wb, bk, y, L.dtype_code(out_dtype, what="out_dtype"),
+               L.stream_ptr(xa.device))
+        ctx.save_for_backward(xa, xb, wb)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xa, xb, wb = ctx.saved_tensors
+        (B, D, H, W, ca), cb, cout = xa.shape, xb.shape[-1], wb.shape[0]
+        dev, st, M = xa.device, L.stream_ptr(xa.device), B * D * H * W
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_w = ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3])
+        dyb = _bf16_2d(dy.reshape(M, cout), M, cout)
+        dxa = dxb = dwk = db = None
+        if need_a or need_b:
+            wt = _weight_t(wb, 27)   # [ca + cb, 27 * cout]: a row block per source
+            if need_a and need_b:
+                dxa, dxb = torch.empty_like(xa), torch.empty_like(xb)
+                gb = _geom(B, (D, H, W), cout, ca + cb, 3, 1, 1, True)
+                L.call("pcs_conv3d_cat_dgrad", gb, dyb, wt, dxa, ca, dxb, cb, L.BF16, st)
+            else:   # one source only: the single-source stencil on that source's rows of W^T
+                c, rows = (ca, wt[:ca]) if need_a else (cb, wt[ca:])
+                dx = torch.empty(B, D, H, W, c, dtype=torch.bfloat16, device=dev)
+                L.call("pcs_conv3d", _geom(B, (D, H, W), cout, c, 3, 1, 1, True), dyb, rows.contiguous(), None, dx,
+                       L.BF16, st)
+                dxa, dxb = (dx, None) if need_a else (None, dx)
+        if need_w:
+            g = _geom(B, (D, H, W), ca + cb, cout, 3, 1, 1, False)
+            nbytes = L.workspace("pcs_conv3d_wgrad_workspace", g)
+            dwk, db = _wgrad("pcs_conv3d_cat_wgrad", (g, xa, ca, xb, cb, dyb), nbytes, 27, ca + cb, cout, ca + cb, cout,
+                             ctx.has_bias, dev)
+        return dxa, dxb, dwk, db, None
+
+
+def conv3d_cat(xa, xb, weight, bias=None, out_dtype=torch.bfloat16):
+    """conv3d(torch.cat([xa, xb], -1), weight, bias, stride=1, padding=1) without the concatenated
+    grid, and bit-identical to it (the same k-step and summation order): xa bf16 [B, D, H, W, CA], xb
+    bf16 [B, D, H, W, CB], weight [Cout, CA + CB, 3, 3, 3] (the concatenated layer's, fp32), bias
+    [Cout] or None.  The forward writes and autograd keeps no [.., CA + CB] tensor, and the backward
+    writes the two input gradients from one stencil pass over dy (None for an input that needs none).
+    The two-source kernels take CA, CB and Cout in multiples of 32; any other width runs torch.cat
+    and conv3d (zero-padded there): those shapes have no two-source path."""
+    if not (xa.is_cuda and xb.is_cuda):
+        raise RuntimeError("pcs_amd conv3d runs on a HIP device only (no CPU fallback)")
+    for name, t in (("xa", xa), ("xb", xb)):
+        if t.dtype != torch.bfloat16 or t.dim() != 5:
+            raise ValueError(f"{name} must be a bf16 [B, D, H, W, C] channels-last voxel grid")
+    if xa.shape[:4] != xb.shape[:4]:
+        raise ValueError(f"xa and xb must share their grid: {list(xa.shape[:4])} and {list(xb.shape[:4])}")
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("out_dtype must be torch.bfloat16 or torch.float32")
+    ca, cb, cout = xa.shape[-1], xb.shape[-1], weight.shape[0]
+    if weight.dim() != 5 or tuple(weight.shape[2:]) != (3, 3, 3):
+        raise ValueError("conv3d_cat is the 3x3x3 form")
+    if weight.shape[1] != ca + cb:
+        raise ValueError(f"weight has {weight.shape[1]} input channels, xa and xb have {ca} + {cb}")
+    if bias is not None and bias.shape != (cout,):
+        raise ValueError(f"bias must be [{cout}]")
+    if ca % DENSE_CH_ALIGN or cb % DENSE_CH_ALIGN or cout % DENSE_CH_ALIGN or ca == 0 or cb == 0:
+        return conv3d(torch.cat([xa, xb], -1), weight, bias, 1, 1, out_dtype)
+    wk = weight.permute(0, 2, 3, 4, 1).reshape(cout, 27 * (ca + cb))
+    return _Conv3dCatFn.apply(xa, xb, wk, bias, out_dtype)
+
+
+class Conv3dCat(torch.nn.Module):
+    """Conv3d(ca + cb, cout, 3, padding=1) applied to the channel concatenation of two grids without
+    building it (conv3d_cat): a U-Net decoder's convolution of (up, skip).  The parameters are exactly
+    nn.Conv3d(ca + cb, cout, 3, padding=1)'s, so state dicts load into Conv3d(ca + cb, cout) and back.
+    Widths off the multiple of 32 run torch.cat and the single-source layer."""
+
+    def __init__(self, ca, cb, cout, bias=True):
+        super().__init__()
+        ref = torch.nn.Conv3d(ca + cb, cout, 3, 1, 1, bias=bias)
+        self.weight, self.bias = ref.weight, ref.bias
+        self.ca, self.cb = ca, cb
+
+    def forward(self, xa, xb, out_dtype=torch.bfloat16):
+        if xa.shape[-1] != self.ca or xb.shape[-1] != self.cb:
+            raise ValueError(f"Conv3dCat({self.ca}, {self.cb}): got {xa.shape[-1]} and {xb.shape[-1]} channels")
+        return conv3d_cat(xa, xb, self.weight, self.bias, out_dtype)
