@@ -56,6 +56,8 @@ _LAZY = {
     "VoxelResBlock": ("voxel_unet", "VoxelResBlock"),
     "VoxelUNet": ("voxel_unet", "VoxelUNet"),
     "VoxelUNetSegmentation": ("voxel_unet", "VoxelUNetSegmentation"),
+    "conv_bn": ("fold", "conv_bn"),
+    "argmax_labels": ("fold", "argmax_labels"),
 }
 
 

@@ -4,7 +4,8 @@ The header is the table: its structs, prototypes, enumerators and PCS_ABI_VERSIO
 at import into the ``ct.Structure`` classes, ``SIGNATURES`` and the constants below, so a new entry
 point is declared in the header only (tests/golden/abi_tables.json records the result).  A header
 of EXT_HEADERS adds entry points of the same library beside pcs.h's (EXT_SIGNATURES), and so does one
-of DENSE_HEADERS, into a table of its own (DENSE_SIGNATURES; tests/golden/abi_tables_dense.json).
+of DENSE_HEADERS, into a table of its own (DENSE_SIGNATURES; tests/golden/abi_tables_dense.json), and
+one of FOLD_HEADERS likewise (FOLD_SIGNATURES; tests/golden/abi_tables_fold.json).
 
 There is no fallback: if the library is missing or fails to load, every GPU entry point
 raises.  ``torch`` is imported first so that the HIP runtime torch ships (same SONAME
@@ -27,6 +28,8 @@ EXT_HEADERS = ("pcs_segmax.h",)
 # The same for the dense voxel U-Net's kernels, kept in a table of their own (DENSE_SIGNATURES) so that
 # EXT_SIGNATURES stays the segmented max's
 DENSE_HEADERS = ("pcs_dense.h",)
+# The same for the folded inference convolutions (pcs_*_affine), in FOLD_SIGNATURES
+FOLD_HEADERS = ("pcs_fold.h",)
 
 _SCALARS = {"int": ct.c_int, "int32_t": ct.c_int32, "int64_t": ct.c_int64, "uint64_t": ct.c_uint64,
             "float": ct.c_float}
@@ -176,8 +179,8 @@ def parse_extension(main_text, ext_text, main=None):
     return f2[len(functions):]
 
 
-_ext_functions, _dense_functions = [], []
-for _hs, _into in ((EXT_HEADERS, _ext_functions), (DENSE_HEADERS, _dense_functions)):
+_ext_functions, _dense_functions, _fold_functions = [], [], []
+for _hs, _into in ((EXT_HEADERS, _ext_functions), (DENSE_HEADERS, _dense_functions), (FOLD_HEADERS, _fold_functions)):
     for _h in _hs:
         with open(HEADER_PATH) as _f, open(os.path.join(os.path.dirname(HEADER_PATH), _h)) as _g:
             _into += parse_extension(_f.read(), _g.read(), (_consts, _structs, _functions))
@@ -185,9 +188,11 @@ for _hs, _into in ((EXT_HEADERS, _ext_functions), (DENSE_HEADERS, _dense_functio
 globals().update(_consts)
 # GemmArgs, WgradArgs, Seg12Args, Conv3dGeom, PoolBwdArgs, HeadArgs; (name, restype, argtypes) of
 # every function the header declares
-_classes, _signatures, _PARAMS = _bind(_structs, _functions + _ext_functions + _dense_functions)
+_classes, _signatures, _PARAMS = _bind(_structs, _functions + _ext_functions + _dense_functions + _fold_functions)
 _n, _m = len(_functions), len(_functions) + len(_ext_functions)
-SIGNATURES, EXT_SIGNATURES, DENSE_SIGNATURES = _signatures[:_n], _signatures[_n:_m], _signatures[_m:]
+_d = _m + len(_dense_functions)
+SIGNATURES, EXT_SIGNATURES, DENSE_SIGNATURES = _signatures[:_n], _signatures[_n:_m], _signatures[_m:_d]
+FOLD_SIGNATURES = _signatures[_d:]
 globals().update({c.__name__: c for c in _classes.values()})
 
 _lib = None
@@ -209,7 +214,7 @@ def load():
             "`python -c 'import __graft_entry__ as g; g.build()'` or "
             "`make -C point-cloud-cnn-segmentation_amd/csrc`.")
     lib = ct.CDLL(path)
-    for name, res, args in SIGNATURES + EXT_SIGNATURES + DENSE_SIGNATURES:
+    for name, res, args in SIGNATURES + EXT_SIGNATURES + DENSE_SIGNATURES + FOLD_SIGNATURES:
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

@@ -28,7 +28,11 @@
 // their output likewise (Out1 / Out2): the two-source layer pcs_sparse_conv_cat*, a decoder's
 // convolution of [up | skip] without the concatenated array, in the same k-step order.
 // The 3x3x3 stride-1 stencil has its own halo-staged kernels (stencil3_kernel, stencil3_wgrad_kernel).
+// Every forward kernel stores its rows through an epilogue policy (EpiNone / EpiAffine below): the
+// pcs_*_affine entry points of include/pcs_fold.h fold an eval-mode BatchNorm (+ residual) (+ ReLU) into
+// the store, for inference.
 #include "../../include/pcs_dense.h"
+#include "../../include/pcs_fold.h"
 #include "kernel_prims.h"
 
 namespace {
@@ -83,6 +87,63 @@ struct Out2 {
     return Y.YB;
   }
 };
+
+// What a forward kernel does to its fp32 accumulators (+ bias) where it stores them, at the three
+// places rows are stored (store_tile, the end of stencil3_kernel, pair_reduce_kernel).  EpiNone:
+// nothing, the plain convolution.  EpiAffine (include/pcs_fold.h): an eval-mode BatchNorm (+ residual)
+// (+ ReLU) folded into the store,
+//   y = act(fmaf(v, scale[c], shift[c]) (+ R[row][c])),  act = relu or the identity
+// which is pcs_sparse_bn_apply's statement in its operation order (an explicit fmaf, then the
+// residual's own add), so a folded layer is bit-identical to that pass run on the convolution's fp32
+// output.  R: rows in Y's dtype, row indexing and leading dimension, or NULL.  relu and R are run-time
+// (uniform) flags: a kernel has one affine instantiation per plain one.  Affine kernels write one
+// array (Out1).
+struct EpiNone { static constexpr bool AFFINE = false; };
+struct EpiAffine {
+  static constexpr bool AFFINE = true;
+  const float *scale, *shift;   // f32 [Cout]
+  const void *R;
+  int relu;
+};
+// a lane's coefficients of N consecutive channels (4 or 8): loaded once per column tile, outside the row loop
+template <int N> struct EpiCoef { float s[N], t[N]; };
+template <int N>
+PCS_DEV EpiCoef<N> epi_coef(const EpiAffine &ep, int c) {
+  EpiCoef<N> k;
+  load_vec<N>(ep.scale, c, k.s);
+  load_vec<N>(ep.shift, c, k.t);
+  return k;
+}
+template <int N> PCS_DEV EpiNone epi_coef(const EpiNone &, int) { return EpiNone{}; }
+// v[0 .. N) = the N channels stored at element offset off of Y (and of R, read in the store's width)
+template <bool OUT_BF16, int N>
+PCS_DEV void epi_apply(const EpiAffine &ep, const EpiCoef<N> &k, int64_t off, float (&v)[N]) {
+#pragma unroll
+  for (int e = 0; e < N; ++e) v[e] = fmaf(v[e], k.s[e], k.t[e]);
+  if (ep.R) {
+    float r[N];
+    if constexpr (OUT_BF16 && N == 4) {
+      const uint2 q = *reinterpret_cast<const uint2 *>(static_cast<const bf16_t *>(ep.R) + off);
+      r[0] = bf2f(q.x & 0xffffu); r[1] = bf2f(q.x >> 16); r[2] = bf2f(q.y & 0xffffu); r[3] = bf2f(q.y >> 16);
+    } else if constexpr (OUT_BF16) {
+      unpack_chunk(*reinterpret_cast<const u32x4 *>(static_cast<const bf16_t *>(ep.R) + off), r);
+    } else {
+      load_vec<N>(static_cast<const float *>(ep.R) + off, 0, r);
+    }
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] += r[e];
+  }
+  if (ep.relu) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = relu(v[e]);
+  }
+}
+// A kernel takes its epilogue as a trailing parameter pack of zero or one EpiAffine, so that the plain
+// kernels keep exactly their parameters; epi_of(ep...) is the pack's epilogue.  The store sites call
+// epi_apply behind an if constexpr: even a call that compiles to nothing there moved the register
+// allocation of ten plain instantiations by 2 to 4 VGPRs; with it they compile to their former figures.
+PCS_DEV EpiNone epi_of() { return EpiNone{}; }
+PCS_DEV EpiAffine epi_of(const EpiAffine &e) { return e; }
 
 // input voxel feeding output voxel (b, z, y, x) through tap (dz, dy, dx); -1 = none (zero)
 PCS_DEV int64_t in_voxel(const pcs_conv3d_geom &g, int b, int z, int y, int x, int dz, int dy, int dx) {
@@ -270,12 +331,17 @@ PCS_DEV void gather_gemm_tile(typename XF::Arg X, int Cin, const bf16_t *__restr
 
 // The forward epilogue on gather_gemm_tile's accumulators: Y[out_row(r)][n0 ..] = acc + bias, 4
 // channels of one row per store (bf16 or fp32); out_row(r) is the output row of tile row r, or -1
-// to skip it.
-template <int BMT, int BNT, bool OUT_BF16, class RowF>
+// to skip it.  ep (EpiNone or EpiAffine) acts on the biased sums before the store.
+template <int BMT, int BNT, bool OUT_BF16, class RowF, class EP = EpiNone>
 PCS_DEV void store_tile(const f32x4 (&acc)[BMT / 32][BNT / 32], RowF out_row, int n0, int Cout,
-                        const float *__restrict__ bias, void *__restrict__ Y) {
+                        const float *__restrict__ bias, void *__restrict__ Y, const EP &ep = EP{}) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int wr = wid >> 1, wc = wid & 1, lr = lane & 15, lg = lane >> 4;
+  decltype(epi_coef<4>(ep, 0)) ek[BNT / 32];
+  if constexpr (EP::AFFINE) {
+#pragma unroll
+    for (int j = 0; j < BNT / 32; ++j) ek[j] = epi_coef<4>(ep, n0 + wc * (BNT / 2) + j * 16 + 4 * lg);
+  }
 #pragma unroll
   for (int i = 0; i < BMT / 32; ++i) {
     const int64_t uo = out_row(wr * (BMT / 2) + i * 16 + lr);
@@ -288,6 +354,7 @@ PCS_DEV void store_tile(const f32x4 (&acc)[BMT / 32][BNT / 32], RowF out_row, in
         const float4 bb = *reinterpret_cast<const float4 *>(bias + co);
         v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
       }
+      if constexpr (EP::AFFINE) epi_apply<OUT_BF16>(ep, ek[j], uo * Cout + co, v);
       if constexpr (OUT_BF16) {
         *reinterpret_cast<uint2 *>(reinterpret_cast<bf16_t *>(Y) + uo * Cout + co) =
             make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
@@ -299,10 +366,10 @@ PCS_DEV void store_tile(const f32x4 (&acc)[BMT / 32][BNT / 32], RowF out_row, in
 }
 
 // The dense gather: rows = output voxels, zero rows off the grid or off the stride lattice
-template <int BMT, int KST, bool OUT_BF16, int BNT = BN>
+template <int BMT, int KST, bool OUT_BF16, int BNT = BN, class... EP>
 __global__ __launch_bounds__(THREADS) void conv3d_kernel(pcs_conv3d_geom g, const bf16_t *__restrict__ X,
                                                          const bf16_t *__restrict__ W, const float *__restrict__ bias,
-                                                         void *__restrict__ Y, int64_t M) {
+                                                         void *__restrict__ Y, int64_t M, EP... ep) {
   constexpr int RPP = THREADS / (KST / 8), HA = BMT / RPP;   // gather_gemm_tile's staging passes
   // class mode (transposed, stride 2): blockIdx.x = tile * 8 + class, rows index the class sub-grid
   const bool cm = g.transposed && g.s == 2;
@@ -355,7 +422,7 @@ __global__ __launch_bounds__(THREADS) void conv3d_kernel(pcs_conv3d_geom g, cons
     decode_class(pc, uo, ob, oz, oy, ox);
     return (((int64_t)ob * g.Do + oz) * g.Ho + oy) * g.Wo + ox;
   };
-  store_tile<BMT, BNT, OUT_BF16>(acc, out_row, n0, g.Cout, bias, Y);
+  store_tile<BMT, BNT, OUT_BF16>(acc, out_row, n0, g.Cout, bias, Y, ep...);
 }
 
 // ---- 3x3x3 stride-1 stencil (both forms) with the input block's halo staged in LDS once per
@@ -373,10 +440,11 @@ constexpr int HIMG = HROWS * 128, WTILE = 64 * 128;        // halo image (64 ch)
 
 PCS_DEV int swz8(int row, int ch) { return ch ^ ((row >> 1) & 7); }
 
-template <int CS, int NT, bool OUT_BF16, class XF = Rows1, class YF = Out1>
+template <int CS, int NT, bool OUT_BF16, class XF = Rows1, class YF = Out1, class... EP>
 __global__ __launch_bounds__(THREADS) void stencil3_kernel(pcs_conv3d_geom g, typename XF::Arg X,
                                                            const bf16_t *__restrict__ W, const float *__restrict__ bias,
-                                                           typename YF::Arg Y) {
+                                                           typename YF::Arg Y, EP... epp) {
+  static_assert(sizeof...(EP) == 0 || !YF::SPLIT, "the affine epilogue writes one array");
   __shared__ __attribute__((aligned(16))) char lds[HIMG + 2 * WTILE];   // 45 KB + 16 KB
   char *halo = lds, *wt = lds + HIMG;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -466,6 +534,12 @@ __global__ __launch_bounds__(THREADS) void stencil3_kernel(pcs_conv3d_geom g, ty
       __syncthreads();
     }
   }
+  const auto ep = epi_of(epp...);
+  decltype(epi_coef<4>(ep, 0)) ek[TJ];
+  if constexpr (sizeof...(EP) != 0) {
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) ek[j] = epi_coef<4>(ep, n0 + wc * (NT / 2) + j * 16 + 4 * lg);
+  }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int r = wr * 64 + i * 16 + lr;
@@ -482,6 +556,7 @@ __global__ __launch_bounds__(THREADS) void stencil3_kernel(pcs_conv3d_geom g, ty
       }
       int cy = co, ld = g.Cout;
       void *y = YF::pick(Y, cy, ld);
+      if constexpr (sizeof...(EP) != 0) epi_apply<OUT_BF16>(ep, ek[j], uo * ld + cy, v);
       if constexpr (OUT_BF16) {
         *reinterpret_cast<uint2 *>(reinterpret_cast<bf16_t *>(y) + uo * ld + cy) =
             make_uint2(pack2bf(v[0], v[1]), pack2bf(v[2], v[3]));
@@ -832,12 +907,13 @@ __global__ __launch_bounds__(256) void conv3d_weight_t_kernel(const bf16_t *__re
 // With flip and W^T (pcs_conv3d_weight_t) this is the input gradient: offset(taps-1-t) =
 // -offset(t) for the centred 3x3x3 taps, so dX[n] = sum_t W_t^T dY[nbr[n][taps-1-t]].
 // X: Rows1 or Rows2 (the two-source forward), Y: Out1 or Out2 (its input gradient to both sources).
-template <int BMT, int KST, bool OUT_BF16, class XF = Rows1, class YF = Out1>
+template <int BMT, int KST, bool OUT_BF16, class XF = Rows1, class YF = Out1, class... EP>
 __global__ __launch_bounds__(THREADS) void sparse_conv_kernel(const int32_t *__restrict__ nbr, int64_t M, int taps,
                                                               typename XF::Arg X, int Cin,
                                                               const bf16_t *__restrict__ W, int Cout,
                                                               const float *__restrict__ bias, typename YF::Arg Y,
-                                                              int flip) {
+                                                              int flip, EP... ep) {
+  static_assert(sizeof...(EP) == 0 || !YF::SPLIT, "the affine epilogue writes one array");
   __shared__ uint32_t tmask;
   __shared__ int tlist[32];
   __shared__ int ntl;
@@ -870,7 +946,7 @@ __global__ __launch_bounds__(THREADS) void sparse_conv_kernel(const int32_t *__r
   int c0 = n0, ld = Cout;
   void *y = YF::pick(Y, c0, ld);
   if constexpr (YF::SPLIT) bias = bias ? bias + (n0 - c0) : nullptr;   // store_tile adds bias[c0 + ..]
-  store_tile<BMT, BN, OUT_BF16>(acc, [&](int r) { return m0 + r < M ? m0 + r : -1; }, c0, ld, bias, y);
+  store_tile<BMT, BN, OUT_BF16>(acc, [&](int r) { return m0 + r < M ? m0 + r : -1; }, c0, ld, bias, y, ep...);
 }
 
 // weight gradient of the sparse convolution: dW[co][t][ci] = sum_m dY[m][co] X[nbr[m][t]][ci];
@@ -1134,10 +1210,11 @@ __global__ __launch_bounds__(THREADS) void pair_gemm_kernel(PairTaps pt, const i
 }
 
 // Y[m][c .. c + 7] = b + sum over taps in order of Z[pair_pos[m][t]] (one thread per 8 channels)
-template <bool OUT_BF16, class YF = Out1>
+template <bool OUT_BF16, class YF = Out1, class... EP>
 __global__ __launch_bounds__(256) void pair_reduce_kernel(const int32_t *__restrict__ ppos, int64_t M, int taps,
                                                           const float *__restrict__ Z, int Cout,
-                                                          const float *__restrict__ bias, typename YF::Arg Y) {
+                                                          const float *__restrict__ bias, typename YF::Arg Y, EP... epp) {
+  static_assert(sizeof...(EP) == 0 || !YF::SPLIT, "the affine epilogue writes one array");
   const int cpr = Cout / 8;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= M * cpr) return;
@@ -1156,6 +1233,13 @@ __global__ __launch_bounds__(256) void pair_reduce_kernel(const int32_t *__restr
   }
   int cy = c, ld = Cout;
   void *y = YF::pick(Y, cy, ld);
+  if constexpr (sizeof...(EP) != 0) {
+    const auto ep = epi_of(epp...);
+    float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+    epi_apply<OUT_BF16>(ep, epi_coef<8>(ep, c), m * ld + cy, v);
+    a = f32x4{v[0], v[1], v[2], v[3]};
+    b = f32x4{v[4], v[5], v[6], v[7]};
+  }
   if constexpr (OUT_BF16) {
     *reinterpret_cast<u32x4 *>(reinterpret_cast<bf16_t *>(y) + m * ld + cy) =
         mk_u32x4(pack2bf(a[0], a[1]), pack2bf(a[2], a[3]), pack2bf(b[0], b[1]), pack2bf(b[2], b[3]));
@@ -1169,13 +1253,13 @@ __global__ __launch_bounds__(256) void pair_reduce_kernel(const int32_t *__restr
 // row has exactly one pair (the up-convolution of a k = 2, s = 2 level, and the down-convolution's
 // input gradient: a fine voxel has one parent and sits at one tap of it).  pair_gemm_kernel's
 // tile with the forward epilogue scattered through pair_out: no Z, no reduce pass.
-template <int KST, bool OUT_BF16>
+template <int KST, bool OUT_BF16, class... EP>
 __global__ __launch_bounds__(THREADS) void pair_rows_kernel(PairTaps pt, const int32_t *__restrict__ pin,
                                                             const int32_t *__restrict__ pout,
                                                             const bf16_t *__restrict__ X, int Cin,
                                                             const bf16_t *__restrict__ W, int Cout,
                                                             const float *__restrict__ bias, int64_t M,
-                                                            void *__restrict__ Y) {
+                                                            void *__restrict__ Y, EP... ep) {
   f32x4 acc[2][2];
   int64_t p0, pend;
   pair_tile<KST, Rows1>(pt, pin, X, Cin, W, 0, acc, p0, pend);
@@ -1184,7 +1268,7 @@ __global__ __launch_bounds__(THREADS) void pair_rows_kernel(PairTaps pt, const i
     const int64_t uo = pout[p0 + r];
     return uo < M ? uo : -1;   // (negative or >= M: not a row of Y, a list that breaks the precondition)
   };
-  store_tile<64, BN, OUT_BF16>(acc, out_row, blockIdx.y * BN, Cout, bias, Y);
+  store_tile<64, BN, OUT_BF16>(acc, out_row, blockIdx.y * BN, Cout, bias, Y, ep...);
 }
 
 // dW_t partial of one pair slice g of tap t: sum over its pairs of dY[pair_out] (x) X[pair_in] into
@@ -1260,19 +1344,20 @@ int launched(const char *who) {
 }
 
 // The launches behind the sparse entry points, after their argument checks: XF is Rows1 or Rows2, YF
-// Out1 or Out2 (the two-source layer's blocks are multiples of 64 channels: 64-deep k-steps).
+// Out1 or Out2 (the two-source layer's blocks are multiples of 64 channels: 64-deep k-steps), ep the
+// forward epilogue (EpiNone, or EpiAffine behind the pcs_*_affine entry points of pcs_fold.h).
 
 // sparse_conv_kernel over M > 0 rows
-template <class XF, class YF>
+template <class XF, class YF, class... EP>
 int launch_sparse_conv(const char *who, const int32_t *nbr, int64_t M, int taps, typename XF::Arg X, int Cin, const void *W,
-                       int Cout, const float *bias, typename YF::Arg Y, int ydtype, int flip, hipStream_t s) {
+                       int Cout, const float *bias, typename YF::Arg Y, int ydtype, int flip, hipStream_t s, EP... ep) {
   const int64_t tiles = (M + 63) / 64;
   if (tiles > 0x7fffffff) return pcs_set_einval(who, "too many rows");
   const dim3 grid((unsigned)tiles, (unsigned)(Cout / BN));
   const bf16_t *Wb = static_cast<const bf16_t *>(W);
 #define PCS_SC(KST, OB) \
-  hipLaunchKernelGGL((sparse_conv_kernel<64, KST, OB, XF, YF>), grid, dim3(THREADS), 0, s, nbr, M, taps, X, Cin, Wb, \
-                     Cout, bias, Y, flip)
+  hipLaunchKernelGGL((sparse_conv_kernel<64, KST, OB, XF, YF, EP...>), grid, dim3(THREADS), 0, s, nbr, M, taps, X, Cin, Wb, \
+                     Cout, bias, Y, flip, ep...)
   if constexpr (XF::SPLIT || YF::SPLIT) {
     if (ydtype == PCS_BF16) PCS_SC(64, true); else PCS_SC(64, false);
   } else {
@@ -1283,10 +1368,10 @@ int launch_sparse_conv(const char *who, const int32_t *nbr, int64_t M, int taps,
 }
 
 // pair_gemm_kernel over the pair tiles into Z, then pair_reduce_kernel over the M rows
-template <class XF, class YF>
+template <class XF, class YF, class... EP>
 int launch_pair_conv(const char *who, const PairTaps &pt, const int32_t *pair_in, const int32_t *pair_pos, int64_t M,
                      typename XF::Arg X, int Cin, const void *W, int Cout, const float *bias, float *Z,
-                     typename YF::Arg Y, int ydtype, int flip, hipStream_t s) {
+                     typename YF::Arg Y, int ydtype, int flip, hipStream_t s, EP... ep) {
   const int taps = pt.taps, tiles = pt.tile_off[taps];
   const bf16_t *Wb = static_cast<const bf16_t *>(W);
   if (tiles > 0) {
@@ -1303,11 +1388,11 @@ int launch_pair_conv(const char *who, const PairTaps &pt, const int32_t *pair_in
   if (n > 0) {
     const dim3 g((unsigned)((n + 255) / 256));
     if (ydtype == PCS_BF16)
-      hipLaunchKernelGGL((pair_reduce_kernel<true, YF>), g, dim3(256), 0, s, pair_pos, M, taps, Z, Cout, bias,
-                         Y);
+      hipLaunchKernelGGL((pair_reduce_kernel<true, YF, EP...>), g, dim3(256), 0, s, pair_pos, M, taps, Z, Cout, bias,
+                         Y, ep...);
     else
-      hipLaunchKernelGGL((pair_reduce_kernel<false, YF>), g, dim3(256), 0, s, pair_pos, M, taps, Z, Cout, bias,
-                         Y);
+      hipLaunchKernelGGL((pair_reduce_kernel<false, YF, EP...>), g, dim3(256), 0, s, pair_pos, M, taps, Z, Cout, bias,
+                         Y, ep...);
     return launched(who);
   }
   return 0;
@@ -1339,9 +1424,9 @@ int launch_sparse_wgrad(const char *who, const int32_t *nbr, int64_t M, int taps
 // two-source layer runs the split geometry of the layer on the concatenated array.
 
 // stencil3_kernel over the 4 x 4 x 8 output blocks
-template <class XF, class YF>
+template <class XF, class YF, class... EP>
 int launch_stencil3(const char *who, const pcs_conv3d_geom &g, typename XF::Arg X, const void *W, const float *bias,
-                    typename YF::Arg Y, int ydtype, hipStream_t s) {
+                    typename YF::Arg Y, int ydtype, hipStream_t s, EP... ep) {
   const int cs = ctile(g.Cin), nt = ctile(g.Cout);
   const int64_t nblk = stencil_blocks(g);
   if (nblk > 0x7fffffff) return pcs_set_einval(who, "grid too large");
@@ -1349,8 +1434,8 @@ int launch_stencil3(const char *who, const pcs_conv3d_geom &g, typename XF::Arg 
   const bf16_t *Ws = static_cast<const bf16_t *>(W);
 #define PCS_S3(CS, NT)                                                                                          \
   do {                                                                                                          \
-    if (ydtype == PCS_BF16) hipLaunchKernelGGL((stencil3_kernel<CS, NT, true, XF, YF>), sg, dim3(THREADS), 0, s, g, X, Ws, bias, Y); \
-    else hipLaunchKernelGGL((stencil3_kernel<CS, NT, false, XF, YF>), sg, dim3(THREADS), 0, s, g, X, Ws, bias, Y);   \
+    if (ydtype == PCS_BF16) hipLaunchKernelGGL((stencil3_kernel<CS, NT, true, XF, YF, EP...>), sg, dim3(THREADS), 0, s, g, X, Ws, bias, Y, ep...); \
+    else hipLaunchKernelGGL((stencil3_kernel<CS, NT, false, XF, YF, EP...>), sg, dim3(THREADS), 0, s, g, X, Ws, bias, Y, ep...);   \
   } while (0)
   if (cs == 64) { if (nt == 64) PCS_S3(64, 64); else PCS_S3(64, 32); }
   else { if (nt == 64) PCS_S3(32, 64); else PCS_S3(32, 32); }
@@ -1371,32 +1456,42 @@ void launch_stencil3_wgrad(const pcs_conv3d_geom &g, typename XF::Arg X, const b
 #undef PCS_SW
 }
 
-}  // namespace
+// what the pcs_*_affine entry points (include/pcs_fold.h) check beyond their twins, or nullptr
+const char *affine_bad(const float *scale, const float *shift, const void *R) {
+  if (!scale || !shift) return "NULL scale or shift";
+  if (reinterpret_cast<uintptr_t>(R) % 16 != 0) return "R must be rows in Y's dtype, 16-byte aligned (or NULL)";
+  return nullptr;
+}
+EpiAffine affine(const float *scale, const float *shift, const void *R, int relu) {
+  return EpiAffine{scale, shift, R, relu != 0};
+}
 
-extern "C" int pcs_conv3d(const pcs_conv3d_geom *g, const void *X, const void *W, const float *bias, void *Y,
-                          int32_t ydtype, pcs_stream_t stream) {
+// pcs_conv3d and pcs_conv3d_affine (who: the entry point, for the error text)
+template <class... EP>
+int conv3d_forward(const char *who, const pcs_conv3d_geom *g, const void *X, const void *W, const float *bias, void *Y,
+                   int32_t ydtype, pcs_stream_t stream, EP... ep) {
   const char *why = nullptr;
-  if (!geom_ok(g, &why)) return pcs_set_einval("pcs_conv3d", why);
-  if (!X || !W || !Y) return pcs_set_einval("pcs_conv3d", "X, W and Y are required");
+  if (!geom_ok(g, &why)) return pcs_set_einval(who, why);
+  if (!X || !W || !Y) return pcs_set_einval(who, "X, W and Y are required");
   if (g->Cin % 32 != 0 || g->Cout % 32 != 0 || g->Cin <= 0 || g->Cout <= 0)
-    return pcs_set_einval("pcs_conv3d", "Cin and Cout must be multiples of 32");
-  if (ydtype != PCS_F32 && ydtype != PCS_BF16) return pcs_set_einval("pcs_conv3d", "Y dtype: PCS_F32 or PCS_BF16");
+    return pcs_set_einval(who, "Cin and Cout must be multiples of 32");
+  if (ydtype != PCS_F32 && ydtype != PCS_BF16) return pcs_set_einval(who, "Y dtype: PCS_F32 or PCS_BF16");
   const int64_t M = out_voxels(*g);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int cs = ctile(g->Cin), nt = ctile(g->Cout);
   if (stencil3(*g))   // halo-staged stencil (both forms)
-    return launch_stencil3<Rows1, Out1>("pcs_conv3d", *g, static_cast<const bf16_t *>(X), W, bias, Y, ydtype, s);
+    return launch_stencil3<Rows1, Out1>(who, *g, static_cast<const bf16_t *>(X), W, bias, Y, ydtype, s, ep...);
   // transposed stride 2: 8 parity classes, tiles of the largest class's sub-grid each.  128-voxel
   // tiles (8 MFMAs per wave per barrier) once there are enough of them to fill the chip
   const int64_t rows_cls = g->transposed && g->s == 2 ? g->B * ((g->Do + 1) / 2) * ((g->Ho + 1) / 2) * ((g->Wo + 1) / 2) : M;
   const int64_t ncb = g->Cout / nt;
   const int bmt = (rows_cls / 128) * ncb * (g->transposed && g->s == 2 ? 8 : 1) >= 2048 ? 128 : 64;
   const int64_t tiles = (rows_cls + bmt - 1) / bmt * (g->transposed && g->s == 2 ? 8 : 1);
-  if (tiles <= 0 || tiles > 0x7fffffff) return pcs_set_einval("pcs_conv3d", "grid too large");
+  if (tiles <= 0 || tiles > 0x7fffffff) return pcs_set_einval(who, "grid too large");
   const dim3 grid((unsigned)tiles, (unsigned)ncb);
   const bf16_t *Xb = static_cast<const bf16_t *>(X), *Wb = static_cast<const bf16_t *>(W);
 #define PCS_C3(BMT, KST, OB, NT) \
-  hipLaunchKernelGGL((conv3d_kernel<BMT, KST, OB, NT>), grid, dim3(THREADS), 0, s, *g, Xb, Wb, bias, Y, M)
+  hipLaunchKernelGGL((conv3d_kernel<BMT, KST, OB, NT, EP...>), grid, dim3(THREADS), 0, s, *g, Xb, Wb, bias, Y, M, ep...)
 #define PCS_C3T(KST, OB)                                                                  \
   do {                                                                                    \
     if (bmt == 128) { if (nt == 64) PCS_C3(128, KST, OB, 64); else PCS_C3(128, KST, OB, 32); } \
@@ -1405,8 +1500,21 @@ extern "C" int pcs_conv3d(const pcs_conv3d_geom *g, const void *X, const void *W
   PCS_KST_OB(cs == 64, ydtype == PCS_BF16, PCS_C3T);
 #undef PCS_C3T
 #undef PCS_C3
-  PCS_CHECK_LAUNCH();
-  return 0;
+  return launched(who);
+}
+
+}  // namespace
+
+extern "C" int pcs_conv3d(const pcs_conv3d_geom *g, const void *X, const void *W, const float *bias, void *Y,
+                          int32_t ydtype, pcs_stream_t stream) {
+  return conv3d_forward(__func__, g, X, W, bias, Y, ydtype, stream);
+}
+
+extern "C" int pcs_conv3d_affine(const pcs_conv3d_geom *g, const void *X, const void *W, const float *bias, void *Y,
+                                 int32_t ydtype, const float *scale, const float *shift, const void *R, int32_t relu,
+                                 pcs_stream_t stream) {
+  if (const char *why = affine_bad(scale, shift, R)) return pcs_set_einval(__func__, why);
+  return conv3d_forward(__func__, g, X, W, bias, Y, ydtype, stream, affine(scale, shift, R, relu));
 }
 
 extern "C" int64_t pcs_conv3d_wgrad_workspace(const pcs_conv3d_geom *g) {
@@ -1460,19 +1568,38 @@ extern "C" int pcs_conv3d_weight_t(const void *W, int32_t Cout, int32_t taps, in
 }
 
 // ---- submanifold sparse convolution (hash-indexed gather; see sparse_conv_kernel)
-extern "C" int pcs_sparse_conv(const int32_t *nbr, int64_t M, int32_t taps, const void *X, int32_t Cin, const void *W,
-                               int32_t Cout, const float *bias, void *Y, int32_t ydtype, int32_t flip,
-                               pcs_stream_t stream) {
+namespace {
+// pcs_sparse_conv and pcs_sparse_conv_affine
+template <class... EP>
+int sparse_conv_forward(const char *who, const int32_t *nbr, int64_t M, int32_t taps, const void *X, int32_t Cin,
+                        const void *W, int32_t Cout, const float *bias, void *Y, int32_t ydtype, int32_t flip,
+                        pcs_stream_t stream, EP... ep) {
   if (!nbr || !X || !W || !Y || M < 0 || taps < 1 || taps > 27 || Cin <= 0 || Cout <= 0 || Cin % KS != 0 ||
       Cout % BN != 0 || (ydtype != PCS_F32 && ydtype != PCS_BF16))
-    return pcs_set_einval("pcs_sparse_conv", "bad arguments (1 <= taps <= 27, Cin % 32 == 0, Cout % 64 == 0, Y f32 | bf16)");
+    return pcs_set_einval(who, "bad arguments (1 <= taps <= 27, Cin % 32 == 0, Cout % 64 == 0, Y f32 | bf16)");
   // flip = 1 reads tap taps - 1 - t for tap t: the input gradient's offset(taps - 1 - t) = -offset(t)
   // holds only for the full centred 27-tap map (or the single centre tap)
   if (flip != 0 && taps != 27 && taps != 1)
-    return pcs_set_einval("pcs_sparse_conv", "flip needs the centred 27-tap neighbour map (or taps == 1)");
+    return pcs_set_einval(who, "flip needs the centred 27-tap neighbour map (or taps == 1)");
   if (M == 0) return 0;
-  return launch_sparse_conv<Rows1, Out1>(__func__, nbr, M, taps, static_cast<const bf16_t *>(X), Cin, W, Cout, bias, Y, ydtype,
-                            flip, reinterpret_cast<hipStream_t>(stream));
+  return launch_sparse_conv<Rows1, Out1>(who, nbr, M, taps, static_cast<const bf16_t *>(X), Cin, W, Cout, bias, Y, ydtype,
+                                         flip, reinterpret_cast<hipStream_t>(stream), ep...);
+}
+}  // namespace
+
+extern "C" int pcs_sparse_conv(const int32_t *nbr, int64_t M, int32_t taps, const void *X, int32_t Cin, const void *W,
+                               int32_t Cout, const float *bias, void *Y, int32_t ydtype, int32_t flip,
+                               pcs_stream_t stream) {
+  return sparse_conv_forward(__func__, nbr, M, taps, X, Cin, W, Cout, bias, Y, ydtype, flip, stream);
+}
+
+extern "C" int pcs_sparse_conv_affine(const int32_t *nbr, int64_t M, int32_t taps, const void *X, int32_t Cin,
+                                      const void *W, int32_t Cout, const float *bias, void *Y, int32_t ydtype,
+                                      int32_t flip, const float *scale, const float *shift, const void *R,
+                                      int32_t relu, pcs_stream_t stream) {
+  if (const char *why = affine_bad(scale, shift, R)) return pcs_set_einval(__func__, why);
+  return sparse_conv_forward(__func__, nbr, M, taps, X, Cin, W, Cout, bias, Y, ydtype, flip, stream,
+                             affine(scale, shift, R, relu));
 }
 
 extern "C" int64_t pcs_sparse_conv_wgrad_workspace(int64_t M, int32_t taps, int32_t Cin, int32_t Cout) {
@@ -1545,47 +1672,79 @@ const char *pair_taps(const int64_t *tap_off, int32_t taps, PairTaps *pt) {
   if (tiles > 0x7fffffff || tap_off[taps] >= ((int64_t)1 << 31)) return "too many pairs";
   return nullptr;
 }
-}  // namespace
 
-extern "C" int pcs_sparse_conv_pairs(const int32_t *pair_in, const int32_t *pair_pos, const int64_t *tap_off, int32_t taps,
-                                     int64_t M, const void *X, int32_t Cin, const void *W, int32_t Cout,
-                                     const float *bias, float *Z, void *Y, int32_t ydtype, int32_t flip,
-                                     pcs_stream_t stream) {
+// pcs_sparse_conv_pairs and pcs_sparse_conv_pairs_affine
+template <class... EP>
+int pairs_forward(const char *who, const int32_t *pair_in, const int32_t *pair_pos, const int64_t *tap_off, int32_t taps,
+                  int64_t M, const void *X, int32_t Cin, const void *W, int32_t Cout, const float *bias, float *Z, void *Y,
+                  int32_t ydtype, int32_t flip, pcs_stream_t stream, EP... ep) {
   PairTaps pt;
   const char *why = pair_taps(tap_off, taps, &pt);
-  if (why) return pcs_set_einval("pcs_sparse_conv_pairs", why);
+  if (why) return pcs_set_einval(who, why);
   if (!pair_pos || !X || !W || !Y || M < 0 || Cin <= 0 || Cout <= 0 || Cin % KS != 0 || Cout % BN != 0 ||
       (ydtype != PCS_F32 && ydtype != PCS_BF16) || (tap_off[taps] > 0 && (!pair_in || !Z)))
-    return pcs_set_einval("pcs_sparse_conv_pairs", "bad arguments (Cin % 32 == 0, Cout % 64 == 0, Y f32 | bf16, Z [P, Cout] f32)");
-  if (flip && taps != 27 && taps != 1)
-    return pcs_set_einval("pcs_sparse_conv_pairs", "flip needs the centred 27-tap neighbour map (or taps == 1)");
-  return launch_pair_conv<Rows1, Out1>(__func__, pt, pair_in, pair_pos, M, static_cast<const bf16_t *>(X), Cin, W, Cout, bias,
-                                       Z, Y, ydtype, flip, reinterpret_cast<hipStream_t>(stream));
+    return pcs_set_einval(who, "bad arguments (Cin % 32 == 0, Cout % 64 == 0, Y f32 | bf16, Z [P, Cout] f32)");
+  if (flip && taps != 27 && taps != 1) return pcs_set_einval(who, "flip needs the centred 27-tap neighbour map (or taps == 1)");
+  return launch_pair_conv<Rows1, Out1>(who, pt, pair_in, pair_pos, M, static_cast<const bf16_t *>(X), Cin, W, Cout, bias,
+                                       Z, Y, ydtype, flip, reinterpret_cast<hipStream_t>(stream), ep...);
 }
 
-extern "C" int pcs_sparse_conv_rows(const int32_t *pair_in, const int32_t *pair_out, const int64_t *tap_off, int32_t taps,
-                                    int64_t M, const void *X, int32_t Cin, const void *W, int32_t Cout,
-                                    const float *bias, void *Y, int32_t ydtype, pcs_stream_t stream) {
+// pcs_sparse_conv_rows and pcs_sparse_conv_rows_affine
+template <class... EP>
+int rows_forward(const char *who, const int32_t *pair_in, const int32_t *pair_out, const int64_t *tap_off, int32_t taps,
+                 int64_t M, const void *X, int32_t Cin, const void *W, int32_t Cout, const float *bias, void *Y,
+                 int32_t ydtype, pcs_stream_t stream, EP... ep) {
   PairTaps pt;
   const char *why = pair_taps(tap_off, taps, &pt);
-  if (why) return pcs_set_einval("pcs_sparse_conv_rows", why);
+  if (why) return pcs_set_einval(who, why);
   if (!X || !W || !Y || M < 0 || Cin <= 0 || Cout <= 0 || Cin % KS != 0 || Cout % BN != 0 ||
       (ydtype != PCS_F32 && ydtype != PCS_BF16) || (tap_off[taps] > 0 && (!pair_in || !pair_out)))
-    return pcs_set_einval("pcs_sparse_conv_rows", "bad arguments (Cin % 32 == 0, Cout % 64 == 0, Y f32 | bf16)");
-  if (tap_off[taps] != M)
-    return pcs_set_einval("pcs_sparse_conv_rows", "every output row needs exactly one pair (tap_off[taps] == M)");
+    return pcs_set_einval(who, "bad arguments (Cin % 32 == 0, Cout % 64 == 0, Y f32 | bf16)");
+  if (tap_off[taps] != M) return pcs_set_einval(who, "every output row needs exactly one pair (tap_off[taps] == M)");
   const int tiles = pt.tile_off[taps];
   if (tiles == 0) return 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)tiles, (unsigned)(Cout / BN));
   const bf16_t *Xb = static_cast<const bf16_t *>(X), *Wb = static_cast<const bf16_t *>(W);
 #define PCS_PR(KST, OB) \
-  hipLaunchKernelGGL((pair_rows_kernel<KST, OB>), grid, dim3(THREADS), 0, s, pt, pair_in, pair_out, Xb, (int)Cin, Wb, \
-                     (int)Cout, bias, M, Y)
+  hipLaunchKernelGGL((pair_rows_kernel<KST, OB, EP...>), grid, dim3(THREADS), 0, s, pt, pair_in, pair_out, Xb, (int)Cin, Wb, \
+                     (int)Cout, bias, M, Y, ep...)
   PCS_KST_OB(Cin % 64 == 0, ydtype == PCS_BF16, PCS_PR);
 #undef PCS_PR
-  PCS_CHECK_LAUNCH();
-  return 0;
+  return launched(who);
+}
+}  // namespace
+
+extern "C" int pcs_sparse_conv_pairs(const int32_t *pair_in, const int32_t *pair_pos, const int64_t *tap_off, int32_t taps,
+                                     int64_t M, const void *X, int32_t Cin, const void *W, int32_t Cout,
+                                     const float *bias, float *Z, void *Y, int32_t ydtype, int32_t flip,
+                                     pcs_stream_t stream) {
+  return pairs_forward(__func__, pair_in, pair_pos, tap_off, taps, M, X, Cin, W, Cout, bias, Z, Y, ydtype, flip, stream);
+}
+
+extern "C" int pcs_sparse_conv_pairs_affine(const int32_t *pair_in, const int32_t *pair_pos, const int64_t *tap_off,
+                                            int32_t taps, int64_t M, const void *X, int32_t Cin, const void *W,
+                                            int32_t Cout, const float *bias, float *Z, void *Y, int32_t ydtype,
+                                            int32_t flip, const float *scale, const float *shift, const void *R,
+                                            int32_t relu, pcs_stream_t stream) {
+  if (const char *why = affine_bad(scale, shift, R)) return pcs_set_einval(__func__, why);
+  return pairs_forward(__func__, pair_in, pair_pos, tap_off, taps, M, X, Cin, W, Cout, bias, Z, Y, ydtype, flip, stream,
+                       affine(scale, shift, R, relu));
+}
+
+extern "C" int pcs_sparse_conv_rows(const int32_t *pair_in, const int32_t *pair_out, const int64_t *tap_off, int32_t taps,
+                                    int64_t M, const void *X, int32_t Cin, const void *W, int32_t Cout,
+                                    const float *bias, void *Y, int32_t ydtype, pcs_stream_t stream) {
+  return rows_forward(__func__, pair_in, pair_out, tap_off, taps, M, X, Cin, W, Cout, bias, Y, ydtype, stream);
+}
+
+extern "C" int pcs_sparse_conv_rows_affine(const int32_t *pair_in, const int32_t *pair_out, const int64_t *tap_off,
+                                           int32_t taps, int64_t M, const void *X, int32_t Cin, const void *W,
+                                           int32_t Cout, const float *bias, void *Y, int32_t ydtype, const float *scale,
+                                           const float *shift, const void *R, int32_t relu, pcs_stream_t stream) {
+  if (const char *why = affine_bad(scale, shift, R)) return pcs_set_einval(__func__, why);
+  return rows_forward(__func__, pair_in, pair_out, tap_off, taps, M, X, Cin, W, Cout, bias, Y, ydtype, stream,
+                      affine(scale, shift, R, relu));
 }
 
 namespace {
@@ -1675,16 +1834,58 @@ const char *cat_args_bad(int64_t M, int taps, int CA, int CB, int Cout, int ydty
 Rows2 rows2(const void *XA, int CA, const void *XB) {
   return Rows2{static_cast<const bf16_t *>(XA), static_cast<const bf16_t *>(XB), CA};
 }
+
+// pcs_sparse_conv_cat and pcs_sparse_conv_cat_affine
+template <class... EP>
+int cat_forward(const char *who, const int32_t *nbr, int64_t M, int32_t taps, const void *XA, int32_t CA, const void *XB,
+                int32_t CB, const void *W, int32_t Cout, const float *bias, void *Y, int32_t ydtype, int32_t flip,
+                pcs_stream_t stream, EP... ep) {
+  if (const char *why = cat_args_bad(M, taps, CA, CB, Cout, ydtype, flip)) return pcs_set_einval(who, why);
+  if (!nbr || !XA || !XB || !W || !Y) return pcs_set_einval(who, "NULL nbr, XA, XB, W or Y");
+  if (M == 0) return 0;
+  return launch_sparse_conv<Rows2, Out1>(who, nbr, M, taps, rows2(XA, CA, XB), CA + CB, W, Cout, bias, Y, ydtype, flip,
+                                         reinterpret_cast<hipStream_t>(stream), ep...);
+}
+
+// pcs_sparse_conv_cat_pairs and pcs_sparse_conv_cat_pairs_affine
+template <class... EP>
+int cat_pairs_forward(const char *who, const int32_t *pair_in, const int32_t *pair_pos, const int64_t *tap_off, int32_t taps,
+                      int64_t M, const void *XA, int32_t CA, const void *XB, int32_t CB, const void *W, int32_t Cout,
+                      const float *bias, float *Z, void *Y, int32_t ydtype, int32_t flip, pcs_stream_t stream, EP... ep) {
+  if (const char *why = cat_args_bad(M, taps, CA, CB, Cout, ydtype, flip)) return pcs_set_einval(who, why);
+  PairTaps pt;
+  if (const char *why = pair_taps(tap_off, taps, &pt)) return pcs_set_einval(who, why);
+  if (!pair_pos || !XA || !XB || !W || !Y || (tap_off[taps] > 0 && (!pair_in || !Z)))
+    return pcs_set_einval(who, "NULL pair_pos, XA, XB, W or Y (or pair_in, Z with pairs)");
+  if (M == 0) return 0;
+  return launch_pair_conv<Rows2, Out1>(who, pt, pair_in, pair_pos, M, rows2(XA, CA, XB), CA + CB, W, Cout, bias, Z, Y, ydtype,
+                                       flip, reinterpret_cast<hipStream_t>(stream), ep...);
+}
 }  // namespace
 
 extern "C" int pcs_sparse_conv_cat(const int32_t *nbr, int64_t M, int32_t taps, const void *XA, int32_t CA, const void *XB,
                                    int32_t CB, const void *W, int32_t Cout, const float *bias, void *Y, int32_t ydtype,
                                    int32_t flip, pcs_stream_t stream) {
-  if (const char *why = cat_args_bad(M, taps, CA, CB, Cout, ydtype, flip)) return pcs_set_einval(__func__, why);
-  if (!nbr || !XA || !XB || !W || !Y) return pcs_set_einval(__func__, "NULL nbr, XA, XB, W or Y");
-  if (M == 0) return 0;
-  return launch_sparse_conv<Rows2, Out1>(__func__, nbr, M, taps, rows2(XA, CA, XB), CA + CB, W, Cout, bias, Y, ydtype, flip,
-                            reinterpret_cast<hipStream_t>(stream));
+  return cat_forward(__func__, nbr, M, taps, XA, CA, XB, CB, W, Cout, bias, Y, ydtype, flip, stream);
+}
+
+extern "C" int pcs_sparse_conv_cat_affine(const int32_t *nbr, int64_t M, int32_t taps, const void *XA, int32_t CA,
+                                          const void *XB, int32_t CB, const void *W, int32_t Cout, const float *bias,
+                                          void *Y, int32_t ydtype, int32_t flip, const float *scale, const float *shift,
+                                          const void *R, int32_t relu, pcs_stream_t stream) {
+  if (const char *why = affine_bad(scale, shift, R)) return pcs_set_einval(__func__, why);
+  return cat_forward(__func__, nbr, M, taps, XA, CA, XB, CB, W, Cout, bias, Y, ydtype, flip, stream,
+                     affine(scale, shift, R, relu));
+}
+
+extern "C" int pcs_sparse_conv_cat_pairs_affine(const int32_t *pair_in, const int32_t *pair_pos, const int64_t *tap_off,
+                                                int32_t taps, int64_t M, const void *XA, int32_t CA, const void *XB,
+                                                int32_t CB, const void *W, int32_t Cout, const float *bias, float *Z,
+                                                void *Y, int32_t ydtype, int32_t flip, const float *scale,
+                                                const float *shift, const void *R, int32_t relu, pcs_stream_t stream) {
+  if (const char *why = affine_bad(scale, shift, R)) return pcs_set_einval(__func__, why);
+  return cat_pairs_forward(__func__, pair_in, pair_pos, tap_off, taps, M, XA, CA, XB, CB, W, Cout, bias, Z, Y, ydtype, flip,
+                           stream, affine(scale, shift, R, relu));
 }
 
 extern "C" int pcs_sparse_conv_cat_dgrad(const int32_t *nbr, int64_t M, int32_t taps, const void *dY, int32_t Cout,
@@ -1713,14 +1914,8 @@ extern "C" int pcs_sparse_conv_cat_pairs(const int32_t *pair_in, const int32_t *
                                          int32_t taps, int64_t M, const void *XA, int32_t CA, const void *XB, int32_t CB,
                                          const void *W, int32_t Cout, const float *bias, float *Z, void *Y, int32_t ydtype,
                                          int32_t flip, pcs_stream_t stream) {
-  if (const char *why = cat_args_bad(M, taps, CA, CB, Cout, ydtype, flip)) return pcs_set_einval(__func__, why);
-  PairTaps pt;
-  if (const char *why = pair_taps(tap_off, taps, &pt)) return pcs_set_einval(__func__, why);
-  if (!pair_pos || !XA || !XB || !W || !Y || (tap_off[taps] > 0 && (!pair_in || !Z)))
-    return pcs_set_einval(__func__, "NULL pair_pos, XA, XB, W or Y (or pair_in, Z with pairs)");
-  if (M == 0) return 0;
-  return launch_pair_conv<Rows2, Out1>(__func__, pt, pair_in, pair_pos, M, rows2(XA, CA, XB), CA + CB, W, Cout, bias, Z, Y, ydtype,
-                          flip, reinterpret_cast<hipStream_t>(stream));
+  return cat_pairs_forward(__func__, pair_in, pair_pos, tap_off, taps, M, XA, CA, XB, CB, W, Cout, bias, Z, Y, ydtype, flip,
+                           stream);
 }
 
 extern "C" int pcs_sparse_conv_cat_dgrad_pairs(const int32_t *pair_in, const int32_t *pair_pos, const int64_t *tap_off,
@@ -1774,13 +1969,27 @@ const char *dense_cat_bad(const pcs_conv3d_geom *g, int cat, int other, int CA, 
   if (stencil_blocks(*g) > 0x7fffffff) return "grid too large";
   return nullptr;
 }
+
+// pcs_conv3d_cat and pcs_conv3d_cat_affine
+template <class... EP>
+int dense_cat_forward(const char *who, const pcs_conv3d_geom *g, const void *XA, int32_t CA, const void *XB, int32_t CB,
+                      const void *W, const float *bias, void *Y, int32_t ydtype, pcs_stream_t stream, EP... ep) {
+  if (const char *why = dense_cat_bad(g, g ? g->Cin : 0, g ? g->Cout : 0, CA, CB, ydtype)) return pcs_set_einval(who, why);
+  if (!XA || !XB || !W || !Y) return pcs_set_einval(who, "NULL XA, XB, W or Y");
+  return launch_stencil3<Rows2, Out1>(who, *g, rows2(XA, CA, XB), W, bias, Y, ydtype, reinterpret_cast<hipStream_t>(stream), ep...);
+}
 }  // namespace
 
 extern "C" int pcs_conv3d_cat(const pcs_conv3d_geom *g, const void *XA, int32_t CA, const void *XB, int32_t CB,
                               const void *W, const float *bias, void *Y, int32_t ydtype, pcs_stream_t stream) {
-  if (const char *why = dense_cat_bad(g, g ? g->Cin : 0, g ? g->Cout : 0, CA, CB, ydtype)) return pcs_set_einval(__func__, why);
-  if (!XA || !XB || !W || !Y) return pcs_set_einval(__func__, "NULL XA, XB, W or Y");
-  return launch_stencil3<Rows2, Out1>(__func__, *g, rows2(XA, CA, XB), W, bias, Y, ydtype, reinterpret_cast<hipStream_t>(stream));
+  return dense_cat_forward(__func__, g, XA, CA, XB, CB, W, bias, Y, ydtype, stream);
+}
+
+extern "C" int pcs_conv3d_cat_affine(const pcs_conv3d_geom *g, const void *XA, int32_t CA, const void *XB, int32_t CB,
+                                     const void *W, const float *bias, void *Y, int32_t ydtype, const float *scale,
+                                     const float *shift, const void *R, int32_t relu, pcs_stream_t stream) {
+  if (const char *why = affine_bad(scale, shift, R)) return pcs_set_einval(__func__, why);
+  return dense_cat_forward(__func__, g, XA, CA, XB, CB, W, bias, Y, ydtype, stream, affine(scale, shift, R, relu));
 }
 
 extern "C" int pcs_conv3d_cat_dgrad(const pcs_conv3d_geom *g, const void *dY, const void *Wt, void *dXA, int32_t CA,

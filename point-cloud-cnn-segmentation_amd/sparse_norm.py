@@ -183,5 +183,12 @@ class SparseResBlock(torch.nn.Module):
         h = self.bn1(self.conv1(x, sv))
         return self.bn2(self.conv2(h, sv), residual=x)
 
+    def infer(self, x, sv: SparseVoxels):
+        """forward in eval mode with each BatchNorm folded into its convolution's store (fold.conv_bn):
+        the running statistics whatever self.training says, no gradient, nothing updated."""
+        from .fold import conv_bn
+        h = conv_bn(self.conv1, self.bn1, x, sv)
+        return conv_bn(self.conv2, self.bn2, h, sv, residual=x)
+
 
 __all__ = ["SparseBatchNorm", "SparseResBlock", "sparse_batch_norm"]

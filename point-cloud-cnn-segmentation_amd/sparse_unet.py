@@ -7,12 +7,15 @@ the voxel vocabulary: the reference has no voxel grid.
     opt = FusedAdam(model)
     logits = model(rb)                                   # rb: RaggedBatch -> fp32 [T, num_classes]
     loss = F.cross_entropy(logits, rb.labels.cuda(), weight=class_weight, ignore_index=-1)
+    labels = model.predict(rb)                           # inference: int64 [T], BatchNorm folded into the convolutions
 
 Every convolution is a HIP kernel on occupied voxels only; the decoder's skip connection is the
 two-source layer (sparse.SubMConv3dCat), so no level builds a concatenated tensor.  model(rb) leaves
 the loss to the caller; model(rb, fused=True) and model.loss(rb, class_weight) run the two per-point
 ends through pcs_amd.pointhead (the lift recomputed inside the voxel mean, the head projected before
-it is interpolated, the cross-entropy where the logits are).  BatchNorm statistics are per device.  The model is a plain nn.Module: FusedAdam
+it is interpolated, the cross-entropy where the logits are).  model.predict(rb) is the inference path
+(pcs_amd.fold): the running statistics, every convolution -> BatchNorm (+ residual) + ReLU as one kernel,
+no gradient, then the argmax.  BatchNorm statistics are per device.  The model is a plain nn.Module: FusedAdam
 (optim.flatten_parameters is generic) works on it; checkpoint.save_checkpoint / load_checkpoint
 rebuild a PointNetSegmentation and do not apply, use state_dict() / load_state_dict().
 """
@@ -100,6 +103,24 @@ class SparseUNet(torch.nn.Module):
             x = self.dec[l](m, pyr.levels[l])
         return x
 
+    def infer(self, x, pyr: SparsePyramid):
+        """forward in eval mode, layer for layer, with every convolution -> BatchNorm pair as one kernel
+        (fold.conv_bn): the running statistics whatever self.training says, no gradient, nothing updated."""
+        from .fold import conv_bn
+        if pyr.depth != self.depth:
+            raise ValueError(f"SparseUNet: {len(self.widths)} widths need a pyramid of depth {self.depth}, got {pyr.depth}")
+        skips = []
+        for l in range(self.depth):
+            e = self.enc[l].infer(x, pyr.levels[l])
+            skips.append(e)
+            x = conv_bn(self.down[l], self.down_bn[l], e, pyr.links[l])
+        x = self.bottom.infer(x, pyr.levels[-1])
+        for l in reversed(range(self.depth)):
+            u = conv_bn(self.up[l], self.up_bn[l], x, pyr.links[l])
+            m = conv_bn(self.merge[l], self.merge_bn[l], u, skips[l], pyr.levels[l])
+            x = self.dec[l].infer(m, pyr.levels[l])
+        return x
+
 
 class SparseUNetSegmentation(torch.nn.Module):
     """Per-point segmentation of a RaggedBatch through the occupied-voxel U-Net: voxelize ->
@@ -161,6 +182,21 @@ class SparseUNetSegmentation(torch.nn.Module):
         dev, pyr, pvm = self._levels(rb)
         x = self._fused_features(rb, dev, pyr, pvm)
         return point_head_loss(x, pvm, self.head.weight, self.head.bias, rb.labels.to(dev), class_weight, return_logits)
+
+    def predict(self, rb: RaggedBatch, return_logits: bool = False):
+        """Inference: int64 labels [T] in the batch's point order, or (labels, fp32 logits [T,
+        num_classes]) with return_logits.  The fused lift, SparseUNet.infer (every BatchNorm folded into
+        its convolution, on the running statistics), point_head and the argmax (pcs_argmax), under
+        torch.no_grad().  self.training, the running buffers and num_batches_tracked are left as they
+        are, so it may be called on a model in train() mode."""
+        from .fold import argmax_labels
+        with torch.no_grad():
+            dev, pyr, pvm = self._levels(rb)
+            fn = point_lift_max if self.lift_mode == "max" else point_lift_mean
+            x = fn(rb.points.to(dev, torch.float32), self.lift.weight, self.lift.bias, pvm)
+            logits = point_head(self.unet.infer(x, pyr), pvm, self.head.weight, self.head.bias)
+            labels = argmax_labels(logits)
+        return (labels, logits) if return_logits else labels
 
 
 __all__ = ["SparsePyramid", "SparseUNet", "SparseUNetSegmentation", "sparse_pyramid"]

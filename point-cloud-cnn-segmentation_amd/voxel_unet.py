@@ -8,6 +8,7 @@ the voxel vocabulary: the reference has no voxel grid.
     opt = FusedAdam(model)
     loss = model.loss(rb, class_weight)                  # rb: RaggedBatch
     logits = model(rb)                                   # fp32 [T, num_classes]
+    labels = model.predict(rb)                           # inference: int64 [T], BatchNorm folded into the convolutions
 
 The module tree and state_dict are SparseUNetSegmentation's for the same widths, and each loads the
 other's: on a fully occupied grid a submanifold convolution is the zero-padded dense convolution, so
@@ -19,7 +20,8 @@ decoder's skip connection is the two-source stencil (voxel.Conv3dCat), so no lev
 concatenated grid.  The row of cell (scene, ix, iy, iz) is (scene * G + ix) * G * G + iy * G + iz, so
 [B * G^3, C] rows and the [B, G, G, G, C] grid are views of each other and the row kernels
 (SparseBatchNorm, the point ends of pcs_amd.pointvoxel / pointhead / segmax) run on the grid
-unchanged.
+unchanged.  model.predict(rb) is the inference path (pcs_amd.fold): the running statistics, every
+convolution -> BatchNorm (+ residual) + ReLU as one kernel, no gradient, then the argmax.
 """
 from __future__ import annotations
 
@@ -80,6 +82,13 @@ class VoxelResBlock(torch.nn.Module):
         h = self.bn1(self.conv1(x))
         return self.bn2(self.conv2(h), residual=x)
 
+    def infer(self, x):
+        """forward in eval mode with each BatchNorm folded into its convolution's store (fold.conv_bn):
+        the running statistics whatever self.training says, no gradient, nothing updated."""
+        from .fold import conv_bn
+        h = conv_bn(self.conv1, self.bn1, x)
+        return conv_bn(self.conv2, self.bn2, h, residual=x)
+
 
 class VoxelUNet(torch.nn.Module):
     """U-Net on a dense bf16 grid [B, G, G, G, widths[0]] in and out, SparseUNet's structure and
@@ -110,10 +119,30 @@ class VoxelUNet(torch.nn.Module):
     def depth(self) -> int:
         return len(self.widths) - 1
 
-    def forward(self, x):
+    def _check_grid(self, x):
         if x.dim() != 5 or any(d % (1 << self.depth) for d in x.shape[1:4]):
             raise ValueError(f"VoxelUNet: a [B, D, H, W, C] grid with D, H, W divisible by 2**{self.depth} is required, "
                              f"got {list(x.shape)}")
+
+    def infer(self, x):
+        """forward in eval mode, layer for layer, with every convolution -> BatchNorm pair as one kernel
+        (fold.conv_bn): the running statistics whatever self.training says, no gradient, nothing updated."""
+        from .fold import conv_bn
+        self._check_grid(x)
+        skips = []
+        for l in range(self.depth):
+            e = self.enc[l].infer(x)
+            skips.append(e)
+            x = conv_bn(self.down[l], self.down_bn[l], e)
+        x = self.bottom.infer(x)
+        for l in reversed(range(self.depth)):
+            u = conv_bn(self.up[l], self.up_bn[l], x)
+            m = conv_bn(self.merge[l], self.merge_bn[l], u, skips[l])
+            x = self.dec[l].infer(m)
+        return x
+
+    def forward(self, x):
+        self._check_grid(x)
         skips = []
         for l in range(self.depth):
             e = self.enc[l](x)
@@ -187,6 +216,23 @@ class VoxelUNetSegmentation(torch.nn.Module):
         dev, B, pvm = self._map(rb)
         x = self._fused_features(rb, dev, B, pvm)
         return point_head_loss(x, pvm, self.head.weight, self.head.bias, rb.labels.to(dev), class_weight, return_logits)
+
+    def predict(self, rb: RaggedBatch, return_logits: bool = False):
+        """Inference: int64 labels [T] in the batch's point order, or (labels, fp32 logits [T,
+        num_classes]) with return_logits.  The fused lift, VoxelUNet.infer (every BatchNorm folded into
+        its convolution, on the running statistics), point_head and the argmax (pcs_argmax), under
+        torch.no_grad().  self.training, the running buffers and num_batches_tracked are left as they
+        are, so it may be called on a model in train() mode."""
+        from .fold import argmax_labels
+        with torch.no_grad():
+            dev, B, pvm = self._map(rb)
+            fn = point_lift_max if self.lift_mode == "max" else point_lift_mean
+            x = fn(rb.points.to(dev, torch.float32), self.lift.weight, self.lift.bias, pvm)
+            G, c = self.grid, x.shape[1]
+            x = self.unet.infer(x.view(B, G, G, G, c)).reshape(B * G * G * G, c)
+            logits = point_head(x, pvm, self.head.weight, self.head.bias)
+            labels = argmax_labels(logits)
+        return (labels, logits) if return_logits else labels
 
 
 __all__ = ["VoxelBatchNorm", "VoxelResBlock", "VoxelUNet", "VoxelUNetSegmentation", "dense_point_map"]
