@@ -197,7 +197,8 @@ int pcs_conv1_wgrad(const pcs_wgrad_args *args, pcs_stream_t stream); /* X = poi
  * stored seg_conv1 output, W = its local half as the forward GEMM saw it, fp32 [512, ldw]):
  *   dX[m]  = dz[m] WaT^T + x[m] H + cvec[b],  cvec[b] = W^T (beta + gamma * scene_bias[b])
  *   dW     = diag(alpha) dz^T x + beta (x) S + diag(gamma) (W G + sum_b scene_bias[b] (x) S_b)
- * with WaT = (diag(alpha) W)^T [64, 512] and H = W^T diag(gamma) W [64, 64] in bf16 (pcs_bn_fold),
+ * with WaT = (diag(alpha) W)^T [64, 512] and H = W^T diag(gamma) W [64, 64] in bf16 (pcs_bn_fold;
+ * row c of H is output column c, as the rows of every pcs_gemm W: H is symmetric, so x H^T = x H),
  * G = x^T x, S_b = per-scene column sums of x (collected by the same pass).  dW (fp32, columns
  * 0..63 of rows with stride ldw, as W) is written, not accumulated.  Workspace
  * (pcs_dgrad_wgrad_folded_workspace() bytes), all fp32: one slab R [512, 64] | G [64, 64] | S [64]

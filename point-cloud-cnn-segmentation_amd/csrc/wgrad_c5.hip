@@ -58,7 +58,10 @@ __global__ __launch_bounds__(THREADS) void wgrad_c5_kernel(pcs_wgrad_args a, int
   const int64_t lo = (int64_t)sis * rows_per_split;
   const int64_t hi = pcs_min64(lo + rows_per_split, N);
   const int64_t sbase = (int64_t)scene * N;
-  const int nsteps = (int)((hi - lo + MS - 1) / MS);   // >= 1 (no empty slices)
+  // <= 0 for an empty trailing slice (a caller's splits_per_scene whose rounded slices pass the scene's
+  // end, hi <= lo): the prologue's DMA clamps to row hi - 1 = N - 1, its transform writes zeros
+  // (rem <= 0), no step runs and the partial is zeros
+  const int nsteps = (int)((hi - lo + MS - 1) / MS);
   const char *Dg = reinterpret_cast<const char *>(a.dZ) + n0 * 2;   // dz5 [M][Cout], this block's columns
   const char *Yg = reinterpret_cast<const char *>(a.X);             // y4 [M][128]
   const int64_t drow = (int64_t)Cout * 2;

@@ -104,13 +104,14 @@ def x_operand(X, s, t, keep, keep_scale, mode, dtype, folded=False):
 # ---------------------------------------------------------------------------------------
 # pcs_wgrad
 # ---------------------------------------------------------------------------------------
-def wgrad_ref(dZ, Y, alpha, beta, gamma, X, s, t, keep, keep_scale, dy_mode, x_mode, dtype, row_weight=None):
+def wgrad_ref(dZ, Y, alpha, beta, gamma, X, s, t, keep, keep_scale, dy_mode, x_mode, dtype, row_weight=None,
+              folded=False):
     """dW[n, k] = sum_m dy[m, n] x[m, k] over all B*N rows; arrays [B, N, C].  row_weight [B, N]
     (None = 1) multiplies each row's term: 0 drops a row, 2 counts it twice (perturbed references
-    of the sensitivity tests only).  Returns dW, its bound, the staged operands and the share of
-    flagged operand elements."""
+    of the sensitivity tests only); folded as x_operand's.  Returns dW, its bound, the staged
+    operands and the share of flagged operand elements."""
     dy = dy_operand(dZ, Y, alpha, beta, gamma, dy_mode, dtype)
-    x = x_operand(X, s, t, keep, keep_scale, x_mode, dtype)
+    x = x_operand(X, s, t, keep, keep_scale, x_mode, dtype, folded=folded)
     B, N, Cout = dy["v"].shape
     M = B * N
     w = np.ones((B, N)) if row_weight is None else f64(row_weight)
@@ -127,25 +128,26 @@ def wgrad_ref(dZ, Y, alpha, beta, gamma, X, s, t, keep, keep_scale, dy_mode, x_m
 # pcs_gemm, PCS_PRO_BWD
 # ---------------------------------------------------------------------------------------
 def dgrad_ref(dZ, Y, alpha, beta, gamma, W, addend, Yp, es, et, keep, keep_scale, mean, rstd, dtype,
-              ge=False, row_weight=None):
+              ge=False, row_weight=None, lds_round=True):
     """The PCS_PRO_BWD input gradient: dgrad_from on dy = alpha dZ + beta + gamma Y as staged."""
     return dgrad_from(dy_operand(dZ, Y, alpha, beta, gamma, PRO_BWD, dtype), W, addend, Yp, es, et, keep,
-                      keep_scale, mean, rstd, dtype, ge=ge, row_weight=row_weight)
+                      keep_scale, mean, rstd, dtype, ge=ge, row_weight=row_weight, lds_round=lds_round)
 
 
 def dgrad_from(dy, W, addend, Yp, es, et, keep, keep_scale, mean, rstd, dtype, bias=None, ge=False,
-               row_weight=None):
+               row_weight=None, lds_round=True):
     """The PCS_EPI_DGRAD / PCS_EPI_RAW epilogue on a staged operand dy (the v / err / flag dict of
     dy_operand or x_operand): v = dy W^T (+ bias) (+ addend), dz = (es Yp + et > 0 ? v keep keep_scale
     : 0) (es = et = None: Yp > 0; keep None: no dropout), per-scene S1 = sum dz and
     S2 = sum dz (Yp - mean) rstd (0 when rstd is None), and raw = dy W^T (the PCS_EPI_RAW output).
     W [Ncols, K], bias [Ncols]; the rest [B, N, C].  The bias joins the accumulator before it is
     rounded to the storage dtype (one more fp32 add).  ge turns the mask into >= 0 and row_weight
-    [B, N] weighs the rows of S1 / S2 (perturbed references of the sensitivity tests only).  Returns
+    [B, N] weighs the rows of S1 / S2 (perturbed references of the sensitivity tests only).
+    lds_round = False: a fused kernel whose accumulator stays fp32 up to the store.  Returns
     the values, their bounds as e_<name>, zmin = the smallest non-zero |es Yp + et| and the share
     of flagged dy elements."""
     W = f64(W)
-    bf = dtype != "f32"
+    bf = dtype != "f32" and lds_round
     acc = dy["v"] @ W.T
     e_acc = sum_bound(W.shape[1], np.abs(dy["v"]) @ np.abs(W).T) * SLACK + dy["err"] @ np.abs(W).T
     r_acc = BF16_U * (np.abs(acc) + e_acc) if bf else 0.0       # bf16: the tile passes through LDS as bf16
@@ -170,7 +172,7 @@ def dgrad_from(dy, W, addend, Yp, es, et, keep, keep_scale, mean, rstd, dtype, b
     nz = np.abs(z[z != 0])
     w = 1.0 if row_weight is None else f64(row_weight)[..., None]
     N = Yp.shape[1]
-    out.update(dz=pre, e_dz=e_pre + (BF16_U * (np.abs(pre) + e_pre) if bf else 0.0), gate=gate,
+    out.update(dz=pre, e_dz=e_pre + (BF16_U * (np.abs(pre) + e_pre) if dtype != "f32" else 0.0), gate=gate,
                zmin=float(nz.min()) if nz.size else np.inf, zeros=int((z == 0).sum()),
                S1=(w * pre).sum(1), e_S1=(w * e_pre).sum(1) + sum_bound(N, (w * np.abs(pre)).sum(1)) * SLACK)
     if rstd is None:

@@ -5,7 +5,8 @@ and against the generic kernel (PCS_FLAG_GENERIC), on ragged scenes (rows not a 
 
     g   = dz5 Ws^T + relu(pa y4 + pb) H4^T + c5        (relu(...) rounded to bf16 as staged)
     dA4 = [es y4 + et > 0] g                            (stored bf16)
-    S1  = sum dA4,  S2 = sum dA4 (y4 - emean) erstd     (per column, summed over the chunks)"""
+    S1  = sum dA4,  S2 = sum dA4 (y4 - emean) erstd     (per scene and column, summed over the
+                                                        scene's chunks: a mix-up of scenes shows)"""
 import ctypes as ct
 
 import pytest
@@ -48,9 +49,9 @@ def _run(B, N, seed, generic=False):
     gg = dz5.double() @ Ws.double().T + a4 @ H4.double().T + c5.double()
     keep = (y4.double() * es.double() + et.double()) > 0
     ref = torch.where(keep, gg, torch.zeros_like(gg))
-    S1 = ref.sum(0)
-    S2 = (ref * (y4.double() - em.double()) * er.double()).sum(0)
-    return out.double().cpu(), stats.sum(0).double().cpu(), ref, S1, S2
+    S1 = ref.view(B, N, 128).sum(1)
+    S2 = (ref * (y4.double() - em.double()) * er.double()).view(B, N, 128).sum(1)
+    return out.double().cpu(), stats.double().view(B, a.chunks_per_scene, 128, 2).sum(1).cpu(), ref, S1, S2
 
 
 @pytest.mark.parametrize("B,N", [(2, 1000), (3, 4096 + 17), (1, 31), (2, 65536 + 5)])
@@ -58,8 +59,9 @@ def test_c5_dgrad_matches_fp64(B, N):
     out, st, ref, S1, S2 = _run(B, N, 7 + N)
     scale = ref.abs().max()
     assert float((out - ref).abs().max() / scale) < 8e-3            # one bf16 rounding of the output
-    assert float((st[:, 0] - S1).abs().max() / S1.abs().max()) < 2e-3
-    assert float((st[:, 1] - S2).abs().max() / S2.abs().max()) < 2e-3
+    assert st.shape == (B, 128, 2) and S1.shape == (B, 128)
+    assert float((st[..., 0] - S1).abs().max() / S1.abs().max()) < 2e-3
+    assert float((st[..., 1] - S2).abs().max() / S2.abs().max()) < 2e-3
 
 
 def test_c5_dgrad_agrees_with_generic_kernel():
