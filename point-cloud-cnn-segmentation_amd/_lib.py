@@ -273,6 +273,14 @@ def call(name, *args):
     return rc
 
 
+def forward_call(name, args, epi, stream):
+    """A forward convolution or its folded twin: name(*args, stream), or with epi = (scale, shift, R, relu)
+    name_affine(*args, *epi, stream).  A one-liner for all seven pairs of include/pcs_fold.h because each
+    twin takes its twin's arguments, then the epilogue, then the stream, which
+    tests/test_fold_abi.py::test_each_twin_takes_its_twins_arguments_plus_the_epilogue pins."""
+    return call(name, *args, stream) if epi is None else call(name + "_affine", *args, *epi, stream)
+
+
 def workspace(name, *args) -> int:
     """The value of a size query (a *_workspace, *_capacity or *_geometry function); a negative
     return raises PcsError with the library's message."""

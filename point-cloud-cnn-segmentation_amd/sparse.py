@@ -42,9 +42,11 @@ import torch
 
 from . import _lib as L
 from .data import RaggedBatch
-from .voxel import CH_ALIGN, VoxelBatch, _box, _bf16_2d, _conv_operands, _pad_channels, _weight_t, _wgrad
+from .voxel import (CH_ALIGN, VoxelBatch, _box, _bf16_2d, _conv_operands, _kernel_weight, _layer, _pad_channels, _unpad,
+                    _weight_t, _wgrad)
 
 TAPS = 27
+K2_TAPS = 8   # the k = 2, s = 2 layers between a level and its coarse level
 # forward / input gradient through the pair lists (gather-GEMM-reduce) when the map has at most
 # this many occupied taps per voxel; above it the tile-gather kernel, whose zero rows are then few
 # and which keeps no per-pair products in memory.  The weight gradient takes the pair lists at
@@ -142,17 +144,17 @@ def sparse_voxels(rb: RaggedBatch, vb: VoxelBatch, lo=(-1.0, -1.0, -1.0), hi=(1.
     return sparse_from_keys(keys, vb.grid)
 
 
-def _conv_taps(nmap, pairs, x, cin, w, cout, bias, y, ydt, flip=0):
+def _conv_taps(nmap, pairs, x, cin, w, cout, bias, y, ydt, flip=0, epi=None):
     """y[m] = b + sum_t W[tw(t)] x[nmap[m][t]]: through the map's pair lists (pairs; Z = per-pair
-    products, fp32) or, with pairs None, in gathered tiles."""
+    products, fp32) or, with pairs None, in gathered tiles; epi: L.forward_call's."""
     (rows, taps), st = nmap.shape, L.stream_ptr(x.device)
     if pairs is None:
-        L.call("pcs_sparse_conv", nmap, rows, taps, x, cin, w, cout, bias, y, ydt, flip, st)
+        L.forward_call("pcs_sparse_conv", (nmap, rows, taps, x, cin, w, cout, bias, y, ydt, flip), epi, st)
         return
     pin, _, ppos, tap_off, P = pairs
     z = torch.empty(max(P, 1), cout, dtype=torch.float32, device=x.device)
-    L.call("pcs_sparse_conv_pairs", pin, ppos, ct.addressof(tap_off), taps, rows, x, cin, w, cout, bias, z, y, ydt,
-           flip, st)
+    L.forward_call("pcs_sparse_conv_pairs", (pin, ppos, ct.addressof(tap_off), taps, rows, x, cin, w, cout, bias, z, y, ydt,
+                                             flip), epi, st)
 
 
 def _sparse_wgrad(nmap, pairs_fn, xk, dyb, cin, cout, has_bias, use_pairs):
@@ -170,31 +172,50 @@ def _sparse_wgrad(nmap, pairs_fn, xk, dyb, cin, cout, has_bias, use_pairs):
     return _wgrad(name, head, nbytes, taps, cin, cout, cin_k, cout_k, has_bias, xk.device)
 
 
+def _sparse_forward(x, wk, bias, at, out_dtype, up=None, epi=None):
+    """The forward of every single-source sparse layer, unfused or with the epilogue epi of fold.conv_bn
+    (the _affine twins): x bf16 [rows_in, Cin], wk the kernel-layout weight [Cout, taps * Cin] (fp32
+    master), at the SparseVoxels of a submanifold layer (up None) or the CoarseLink of a down (up False)
+    or up (up True) layer.  The gather runs through the map's pair lists or in tiles, as at.use_pairs()
+    says; the up map has one tap per output row and runs pcs_sparse_conv_rows.  Returns (y, xk, wb,
+    whether the pair lists carried it): y without the padded channels, and the operands as the kernel
+    read them, which the backward keeps."""
+    nmap, rows_in = (at.nbr, at.nbr.shape[0]) if up is None else (at.up, at.coarse) if up else (at.child, at.fine)
+    taps = TAPS if up is None else K2_TAPS
+    if not x.is_cuda:
+        raise RuntimeError("pcs_amd sparse conv runs on a HIP device only (no CPU fallback)")
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.shape[0] != rows_in or nmap.shape[1] != taps:
+        raise ValueError("x must be bf16 [V, C] with a [V, 27] neighbour map" if up is None else
+                         f"x must be bf16 [{rows_in}, C]: the {'coarse' if up else 'fine'} voxels of the link")
+    rows, cin, cout = nmap.shape[0], x.shape[1], wk.shape[0]
+    if wk.shape[1] != taps * cin:
+        raise ValueError(f"weight has {wk.shape[1] // taps} input channels, x has {cin}")
+    xk, wb, bk, cin_k, cout_k = _conv_operands(x, wk, bias, taps, CH_ALIGN)
+    epi = epi and epi(cout, cout_k, (rows, cout), x.device)
+    y = torch.empty(rows, cout_k, dtype=out_dtype, device=x.device)
+    ydt = L.dtype_code(out_dtype, what="out_dtype")
+    pairs = False
+    if up:
+        _conv_rows(at, xk, cin_k, wb, cout_k, bk, y, ydt, epi)
+    else:
+        pairs = at.use_pairs()
+        _conv_taps(nmap, (at.down_pairs() if up is False else at.pairs()) if pairs else None, xk, cin_k, wb, cout_k, bk, y,
+                   ydt, 0, epi)
+    return _unpad(y, cout), xk, wb, pairs
+
+
 class _SubMConvFn(torch.autograd.Function):
     """y = b + sum_t W_t x[nbr[:, t]] with w in kernel layout [Cout, 27 * Cin] (fp32 master);
     channel counts off the 64 multiple run zero-padded (exact, as voxel._Conv3dFn)."""
 
     @staticmethod
     def forward(ctx, x, wk, bias, sv, out_dtype):
-        nbr = sv.nbr
-        if not x.is_cuda:
-            raise RuntimeError("pcs_amd sparse conv runs on a HIP device only (no CPU fallback)")
-        if x.dtype != torch.bfloat16 or x.dim() != 2 or nbr.shape != (x.shape[0], TAPS):
-            raise ValueError("x must be bf16 [V, C] with a [V, 27] neighbour map")
-        V, cin = x.shape
-        cout = wk.shape[0]
-        if wk.shape[1] != TAPS * cin:
-            raise ValueError(f"weight has {wk.shape[1] // TAPS} input channels, x has {cin}")
-        xk, wb, bk, cin_k, cout_k = _conv_operands(x, wk, bias, TAPS, CH_ALIGN)
-        y = torch.empty(V, cout_k, dtype=out_dtype, device=x.device)
-        pairs = sv.use_pairs()
-        _conv_taps(nbr, sv.pairs() if pairs else None, xk, cin_k, wb, cout_k, bk, y,
-                   L.dtype_code(out_dtype, what="out_dtype"))
-        ctx.save_for_backward(xk, wb, nbr)
-        ctx.sv, ctx.pairs = sv, pairs
-        ctx.wpairs = PAIR_WGRAD and V > 0 and cin_k * cout_k <= PAIR_WGRAD_MAX_CH2
-        ctx.cfg = (bias is not None, cin, cout)
-        return y if cout_k == cout else y[:, :cout].contiguous()
+        y, xk, wb, ctx.pairs = _sparse_forward(x, wk, bias, sv, out_dtype)
+        ctx.save_for_backward(xk, wb, sv.nbr)
+        ctx.sv = sv
+        ctx.wpairs = PAIR_WGRAD and xk.shape[0] > 0 and xk.shape[1] * wb.shape[0] <= PAIR_WGRAD_MAX_CH2
+        ctx.cfg = (bias is not None, x.shape[1], wk.shape[0])
+        return y
 
     @staticmethod
     def backward(ctx, dy):
@@ -215,14 +236,17 @@ class _SubMConvFn(torch.autograd.Function):
         return dx, dwk, db, None, None
 
 
+def _submanifold_conv3d(x, weight, sv, bias, out_dtype, epi=None):
+    """submanifold_conv3d, or (epi) the same layer under fold.conv_bn's epilogue."""
+    if tuple(weight.shape[2:]) != (3, 3, 3):
+        raise ValueError("submanifold_conv3d is the 3x3x3 form")
+    return _layer(_SubMConvFn, _sparse_forward, epi, x, _kernel_weight(weight), bias, sv, out_dtype)
+
+
 def submanifold_conv3d(x, weight, sv: SparseVoxels, bias=None, out_dtype=torch.bfloat16):
     """3x3x3 submanifold convolution of per-voxel features x (bf16 [V, Cin]); weight [Cout, Cin,
     3, 3, 3] (torch Conv3d layout, fp32), bias [Cout] or None."""
-    cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
-    if k != 3 or tuple(weight.shape[2:]) != (3, 3, 3):
-        raise ValueError("submanifold_conv3d is the 3x3x3 form")
-    wk = weight.permute(0, 2, 3, 4, 1).reshape(cout, TAPS * cin)
-    return _SubMConvFn.apply(x, wk, bias, sv, out_dtype)
+    return _submanifold_conv3d(x, weight, sv, bias, out_dtype)
 
 
 class SubMConv3d(torch.nn.Module):
@@ -235,21 +259,24 @@ class SubMConv3d(torch.nn.Module):
         ref = torch.nn.Conv3d(cin, cout, 3, 1, 1, bias=bias)
         self.weight, self.bias = ref.weight, ref.bias
 
+    def _conv(self, epi, x, sv, out_dtype):   # forward, or with epi the layer under fold.conv_bn
+        return _submanifold_conv3d(x, self.weight, sv, self.bias, out_dtype, epi)
+
     def forward(self, x, sv: SparseVoxels, out_dtype=torch.bfloat16):
-        return submanifold_conv3d(x, self.weight, sv, self.bias, out_dtype)
+        return self._conv(None, x, sv, out_dtype)
 
 
 # ---- the two-source layer: the submanifold convolution of [xa | xb] without the concatenation
-def _conv_taps_cat(nmap, pairs, xa, ca, xb, cb, w, cout, bias, y, ydt):
+def _conv_taps_cat(nmap, pairs, xa, ca, xb, cb, w, cout, bias, y, ydt, epi=None):
     """_conv_taps on x = [xa | xb] along channels (pcs_sparse_conv_cat, pcs_sparse_conv_cat_pairs)."""
     (rows, taps), st = nmap.shape, L.stream_ptr(xa.device)
     if pairs is None:
-        L.call("pcs_sparse_conv_cat", nmap, rows, taps, xa, ca, xb, cb, w, cout, bias, y, ydt, 0, st)
+        L.forward_call("pcs_sparse_conv_cat", (nmap, rows, taps, xa, ca, xb, cb, w, cout, bias, y, ydt, 0), epi, st)
         return
     pin, _, ppos, tap_off, P = pairs
     z = torch.empty(max(P, 1), cout, dtype=torch.float32, device=xa.device)
-    L.call("pcs_sparse_conv_cat_pairs", pin, ppos, ct.addressof(tap_off), taps, rows, xa, ca, xb, cb, w, cout, bias, z,
-           y, ydt, 0, st)
+    L.forward_call("pcs_sparse_conv_cat_pairs", (pin, ppos, ct.addressof(tap_off), taps, rows, xa, ca, xb, cb, w, cout, bias,
+                                                 z, y, ydt, 0), epi, st)
 
 
 def _dgrad_taps_cat(nmap, pairs, dyb, cout, wt, dxa, ca, dxb, cb):
@@ -281,6 +308,23 @@ def _sparse_wgrad_cat(nmap, pairs_fn, xa, xb, dyb, has_bias, use_pairs):
     return _wgrad(name, head, nbytes, taps, cin, cout, cin, cout, has_bias, xa.device)
 
 
+def _sparse_cat_forward(xa, xb, wk, bias, sv, out_dtype, epi=None):
+    """_sparse_forward on [xa | xb] along channels, ca, cb and cout multiples of 64 (pcs_sparse_conv_cat*;
+    their _affine twins with the epilogue epi).  An empty level launches nothing.  Returns (y, xa, xb,
+    wb, whether the pair lists carried it)."""
+    V, ca, cb, cout = xa.shape[0], xa.shape[1], xb.shape[1], wk.shape[0]
+    xa, xb = xa.contiguous(), xb.contiguous()
+    wb = _bf16_2d(wk, cout, TAPS * (ca + cb))
+    bk = None if bias is None else bias.float().contiguous()
+    epi = epi and epi(cout, cout, (V, cout), xa.device)
+    y = torch.empty(V, cout, dtype=out_dtype, device=xa.device)
+    pairs = sv.use_pairs()
+    if V > 0:
+        _conv_taps_cat(sv.nbr, sv.pairs() if pairs else None, xa, ca, xb, cb, wb, cout, bk, y,
+                       L.dtype_code(out_dtype, what="out_dtype"), epi)
+    return y, xa, xb, wb, pairs
+
+
 class _SubMConvCatFn(torch.autograd.Function):
     """_SubMConvFn on x = [xa | xb] (ca, cb and cout multiples of 64), which is never built: the
     kernels read the two arrays, autograd keeps xa and xb themselves, and one gather pass over dy
@@ -288,19 +332,10 @@ class _SubMConvCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xa, xb, wk, bias, sv, out_dtype):
-        nbr = sv.nbr
-        V, ca, cb, cout = xa.shape[0], xa.shape[1], xb.shape[1], wk.shape[0]
-        xa, xb = xa.contiguous(), xb.contiguous()
-        wb = _bf16_2d(wk, cout, TAPS * (ca + cb))
-        bk = None if bias is None else bias.float().contiguous()
-        y = torch.empty(V, cout, dtype=out_dtype, device=xa.device)
-        pairs = sv.use_pairs()
-        if V > 0:
-            _conv_taps_cat(nbr, sv.pairs() if pairs else None, xa, ca, xb, cb, wb, cout, bk, y,
-                           L.dtype_code(out_dtype, what="out_dtype"))
-        ctx.save_for_backward(xa, xb, wb, nbr)
-        ctx.sv, ctx.pairs = sv, pairs
-        ctx.wpairs = PAIR_WGRAD and V > 0 and (ca + cb) * cout <= PAIR_WGRAD_MAX_CH2
+        y, xa, xb, wb, ctx.pairs = _sparse_cat_forward(xa, xb, wk, bias, sv, out_dtype)
+        ctx.save_for_backward(xa, xb, wb, sv.nbr)
+        ctx.sv = sv
+        ctx.wpairs = PAIR_WGRAD and xa.shape[0] > 0 and (xa.shape[1] + xb.shape[1]) * wb.shape[0] <= PAIR_WGRAD_MAX_CH2
         ctx.has_bias = bias is not None
         return y
 
@@ -333,14 +368,9 @@ class _SubMConvCatFn(torch.autograd.Function):
         return dxa, dxb, dwk, db, None, None
 
 
-def submanifold_conv3d_cat(xa, xb, weight, sv: SparseVoxels, bias=None, out_dtype=torch.bfloat16):
-    """submanifold_conv3d(torch.cat([xa, xb], 1), weight, sv, bias, out_dtype) without the
-    concatenated tensor, and bit-identical to it (the same k-step and summation order): xa bf16
-    [V, CA], xb bf16 [V, CB], weight [Cout, CA + CB, 3, 3, 3] (the concatenated layer's, fp32), bias
-    [Cout] or None.  The forward writes and autograd keeps no [V, CA + CB] tensor, and the backward
-    writes the two input gradients from one gather pass over dy (None for an input that needs none).
-    The two-source kernels take CA, CB and Cout in multiples of 64; any other width runs torch.cat
-    and submanifold_conv3d (zero-padded there): those shapes have no two-source path."""
+def _submanifold_conv3d_cat(xa, xb, weight, sv, bias, out_dtype, epi=None):
+    """submanifold_conv3d_cat, or (epi) the same layer, with the same torch.cat fall-back, under
+    fold.conv_bn's epilogue."""
     if not (xa.is_cuda and xb.is_cuda):
         raise RuntimeError("pcs_amd sparse conv runs on a HIP device only (no CPU fallback)")
     V = sv.nbr.shape[0]
@@ -357,9 +387,19 @@ def submanifold_conv3d_cat(xa, xb, weight, sv: SparseVoxels, bias=None, out_dtyp
     if bias is not None and bias.shape != (cout,):
         raise ValueError(f"bias must be [{cout}]")
     if ca % CH_ALIGN or cb % CH_ALIGN or cout % CH_ALIGN or ca == 0 or cb == 0:
-        return submanifold_conv3d(torch.cat([xa, xb], 1), weight, sv, bias, out_dtype)
-    wk = weight.permute(0, 2, 3, 4, 1).reshape(cout, TAPS * (ca + cb))
-    return _SubMConvCatFn.apply(xa, xb, wk, bias, sv, out_dtype)
+        return _submanifold_conv3d(torch.cat([xa, xb], 1), weight, sv, bias, out_dtype, epi)
+    return _layer(_SubMConvCatFn, _sparse_cat_forward, epi, xa, xb, _kernel_weight(weight), bias, sv, out_dtype)
+
+
+def submanifold_conv3d_cat(xa, xb, weight, sv: SparseVoxels, bias=None, out_dtype=torch.bfloat16):
+    """submanifold_conv3d(torch.cat([xa, xb], 1), weight, sv, bias, out_dtype) without the
+    concatenated tensor, and bit-identical to it (the same k-step and summation order): xa bf16
+    [V, CA], xb bf16 [V, CB], weight [Cout, CA + CB, 3, 3, 3] (the concatenated layer's, fp32), bias
+    [Cout] or None.  The forward writes and autograd keeps no [V, CA + CB] tensor, and the backward
+    writes the two input gradients from one gather pass over dy (None for an input that needs none).
+    The two-source kernels take CA, CB and Cout in multiples of 64; any other width runs torch.cat
+    and submanifold_conv3d (zero-padded there): those shapes have no two-source path."""
+    return _submanifold_conv3d_cat(xa, xb, weight, sv, bias, out_dtype)
 
 
 class SubMConv3dCat(torch.nn.Module):
@@ -374,16 +414,16 @@ class SubMConv3dCat(torch.nn.Module):
         self.weight, self.bias = ref.weight, ref.bias
         self.ca, self.cb = ca, cb
 
-    def forward(self, xa, xb, sv: SparseVoxels, out_dtype=torch.bfloat16):
+    def _conv(self, epi, xa, xb, sv, out_dtype):
         if xa.shape[-1] != self.ca or xb.shape[-1] != self.cb:
             raise ValueError(f"SubMConv3dCat({self.ca}, {self.cb}): got {xa.shape[-1]} and {xb.shape[-1]} channels")
-        return submanifold_conv3d_cat(xa, xb, self.weight, sv, self.bias, out_dtype)
+        return _submanifold_conv3d_cat(xa, xb, self.weight, sv, self.bias, out_dtype, epi)
+
+    def forward(self, xa, xb, sv: SparseVoxels, out_dtype=torch.bfloat16):
+        return self._conv(None, xa, xb, sv, out_dtype)
 
 
 # ---- stride-2 down / up convolutions (k = 2, s = 2) between a fine level and its coarse level
-K2_TAPS = 8
-
-
 @dataclass
 class CoarseLink:
     """The maps between the voxels of a level (grid G, even) and of its coarse level (G / 2): a
@@ -448,12 +488,12 @@ def coarsen(sv: SparseVoxels):
     return svc, CoarseLink(child, parent, tap, up, V, Vc)
 
 
-def _conv_rows(link, x, cin, w, cout, bias, y, ydt):
-    """y[f] = b + W[tap[f]] x[parent[f]]: one tap per output row (pcs_sparse_conv_rows)."""
+def _conv_rows(link, x, cin, w, cout, bias, y, ydt, epi=None):
+    """y[f] = b + W[tap[f]] x[parent[f]]: one tap per output row (pcs_sparse_conv_rows); epi: L.forward_call's."""
     pin, pout, _, tap_off, P = link.up_pairs()
     assert P == link.fine, "the up map has one pair per fine voxel"
-    L.call("pcs_sparse_conv_rows", pin, pout, ct.addressof(tap_off), K2_TAPS, link.fine, x, cin, w, cout, bias, y, ydt,
-           L.stream_ptr(x.device))
+    L.forward_call("pcs_sparse_conv_rows", (pin, pout, ct.addressof(tap_off), K2_TAPS, link.fine, x, cin, w, cout, bias, y,
+                                            ydt), epi, L.stream_ptr(x.device))
 
 
 def _conv_cells(link, x, cin, w, cout, bias, y, ydt):
@@ -469,26 +509,15 @@ class _StrideConvFn(torch.autograd.Function):
     The weight gradient sums dy[out] (x) x[in] over the pairs of the forward's map."""
 
     @staticmethod
-    def forward(ctx, x, wk, bias, link, up, out_dtype):
-        if not x.is_cuda:
-            raise RuntimeError("pcs_amd sparse conv runs on a HIP device only (no CPU fallback)")
-        rows_in, rows_out = (link.coarse, link.fine) if up else (link.fine, link.coarse)
-        if x.dtype != torch.bfloat16 or x.dim() != 2 or x.shape[0] != rows_in:
-            raise ValueError(f"x must be bf16 [{rows_in}, C]: the {'coarse' if up else 'fine'} voxels of the link")
-        cin, cout = x.shape[1], wk.shape[0]
-        if wk.shape[1] != K2_TAPS * cin:
-            raise ValueError(f"weight has {wk.shape[1] // K2_TAPS} input channels, x has {cin}")
-        xk, wb, bk, cin_k, cout_k = _conv_operands(x, wk, bias, K2_TAPS, CH_ALIGN)
-        y = torch.empty(rows_out, cout_k, dtype=out_dtype, device=x.device)
-        ydt = L.dtype_code(out_dtype, what="out_dtype")
-        (_conv_rows if up else _conv_cells)(link, xk, cin_k, wb, cout_k, bk, y, ydt)
+    def forward(ctx, x, wk, bias, link, out_dtype, up):
+        y, xk, wb, _ = _sparse_forward(x, wk, bias, link, out_dtype, up)
         ctx.save_for_backward(xk, wb)
         ctx.link, ctx.up = link, up
         # the up map's tile-gather weight gradient would run 8 taps for the one each row has: the
         # up layer takes the pair lists at every width
-        ctx.wpairs = up or (PAIR_WGRAD and cin_k * cout_k <= PAIR_WGRAD_MAX_CH2)
-        ctx.cfg = (bias is not None, cin, cout)
-        return y if cout_k == cout else y[:, :cout].contiguous()
+        ctx.wpairs = up or (PAIR_WGRAD and xk.shape[1] * wb.shape[0] <= PAIR_WGRAD_MAX_CH2)
+        ctx.cfg = (bias is not None, x.shape[1], wk.shape[0])
+        return y
 
     @staticmethod
     def backward(ctx, dy):
@@ -511,17 +540,21 @@ class _StrideConvFn(torch.autograd.Function):
         return dx, dwk, db, None, None, None
 
 
+def _stride_conv3d(x, weight, link, bias, out_dtype, up, epi=None):
+    """sparse_conv3d_down or (up) sparse_conv_transpose3d_up, or (epi) the same layer under fold.conv_bn's
+    epilogue."""
+    if tuple(weight.shape[2:]) != (2, 2, 2):
+        raise ValueError(f"{'sparse_conv_transpose3d_up' if up else 'sparse_conv3d_down'} is the 2x2x2, stride-2 form")
+    return _layer(_StrideConvFn, _sparse_forward, epi, x, _kernel_weight(weight, up), bias, link, out_dtype, up)
+
+
 def sparse_conv3d_down(x_fine, weight, link: CoarseLink, bias=None, out_dtype=torch.bfloat16):
     """k = 2, s = 2 convolution from the fine voxels of link to its coarse voxels: x_fine bf16
     [Vf, Cin], weight [Cout, Cin, 2, 2, 2] (torch Conv3d layout, fp32), bias [Cout] or None; returns
     [Vc, Cout].  On a dense grid that is zero off the occupied fine voxels, the output at the
     coarse voxels equals Conv3d(k=2, s=2)'s there; every other coarse site would hold the bias
     alone and is not represented."""
-    cout, cin = weight.shape[0], weight.shape[1]
-    if tuple(weight.shape[2:]) != (2, 2, 2):
-        raise ValueError("sparse_conv3d_down is the 2x2x2, stride-2 form")
-    wk = weight.permute(0, 2, 3, 4, 1).reshape(cout, K2_TAPS * cin)
-    return _StrideConvFn.apply(x_fine, wk, bias, link, False, out_dtype)
+    return _stride_conv3d(x_fine, weight, link, bias, out_dtype, False)
 
 
 def sparse_conv_transpose3d_up(x_coarse, weight, link: CoarseLink, bias=None, out_dtype=torch.bfloat16):
@@ -531,11 +564,7 @@ def sparse_conv_transpose3d_up(x_coarse, weight, link: CoarseLink, bias=None, ou
     the output at the fine occupied voxels equals ConvTranspose3d(k=2, s=2)'s there.  It takes the
     link of the encoder (an inverse convolution): the decoder returns to exactly the encoder's
     voxel set, the other fine sites of an occupied cell are not represented."""
-    cin, cout = weight.shape[0], weight.shape[1]
-    if tuple(weight.shape[2:]) != (2, 2, 2):
-        raise ValueError("sparse_conv_transpose3d_up is the 2x2x2, stride-2 form")
-    wk = weight.permute(1, 2, 3, 4, 0).reshape(cout, K2_TAPS * cin)
-    return _StrideConvFn.apply(x_coarse, wk, bias, link, True, out_dtype)
+    return _stride_conv3d(x_coarse, weight, link, bias, out_dtype, True)
 
 
 class SparseDownConv3d(torch.nn.Module):
@@ -546,8 +575,11 @@ class SparseDownConv3d(torch.nn.Module):
         ref = torch.nn.Conv3d(cin, cout, 2, 2, bias=bias)
         self.weight, self.bias = ref.weight, ref.bias
 
+    def _conv(self, epi, x, link, out_dtype):
+        return _stride_conv3d(x, self.weight, link, self.bias, out_dtype, False, epi)
+
     def forward(self, x, link: CoarseLink, out_dtype=torch.bfloat16):
-        return sparse_conv3d_down(x, self.weight, link, self.bias, out_dtype)
+        return self._conv(None, x, link, out_dtype)
 
 
 class SparseUpConv3d(torch.nn.Module):
@@ -559,8 +591,11 @@ class SparseUpConv3d(torch.nn.Module):
         ref = torch.nn.ConvTranspose3d(cin, cout, 2, 2, bias=bias)
         self.weight, self.bias = ref.weight, ref.bias
 
+    def _conv(self, epi, x, link, out_dtype):
+        return _stride_conv3d(x, self.weight, link, self.bias, out_dtype, True, epi)
+
     def forward(self, x, link: CoarseLink, out_dtype=torch.bfloat16):
-        return sparse_conv_transpose3d_up(x, self.weight, link, self.bias, out_dtype)
+        return self._conv(None, x, link, out_dtype)
 
 
 __all__ = ["CH_ALIGN", "CoarseLink", "SparseDownConv3d", "SparseUpConv3d", "SparseVoxels", "SubMConv3d", "SubMConv3dCat",

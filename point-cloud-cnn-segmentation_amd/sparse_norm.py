@@ -170,6 +170,11 @@ class SparseBatchNorm(torch.nn.BatchNorm1d):
         return super().extra_repr() + f", relu={self.relu}"
 
 
+def conv_then_bn(conv, bn, *inputs, residual=None):
+    """The unfused layer, bn(conv(*inputs), residual), with fold.conv_bn's signature."""
+    return bn(conv(*inputs), residual=residual)
+
+
 class SparseResBlock(torch.nn.Module):
     """SubMConv3d -> BN+ReLU -> SubMConv3d -> BN(+ x)+ReLU on bf16 per-voxel features [V, channels],
     identity shortcut.  The convolutions carry no bias: BatchNorm cancels it."""
@@ -179,16 +184,20 @@ class SparseResBlock(torch.nn.Module):
         self.conv1, self.bn1 = SubMConv3d(channels, channels, bias=False), SparseBatchNorm(channels, relu=True)
         self.conv2, self.bn2 = SubMConv3d(channels, channels, bias=False), SparseBatchNorm(channels, relu=True)
 
+    def _walk(self, layer, x, *at):
+        """The block with layer(conv, bn, *inputs, residual=None) as its two layers: conv_then_bn or
+        fold.conv_bn.  at: what the convolutions take after x (VoxelResBlock's take nothing)."""
+        h = layer(self.conv1, self.bn1, x, *at)
+        return layer(self.conv2, self.bn2, h, *at, residual=x)
+
     def forward(self, x, sv: SparseVoxels):
-        h = self.bn1(self.conv1(x, sv))
-        return self.bn2(self.conv2(h, sv), residual=x)
+        return self._walk(conv_then_bn, x, sv)
 
     def infer(self, x, sv: SparseVoxels):
         """forward in eval mode with each BatchNorm folded into its convolution's store (fold.conv_bn):
         the running statistics whatever self.training says, no gradient, nothing updated."""
-        from .fold import conv_bn
-        h = conv_bn(self.conv1, self.bn1, x, sv)
-        return conv_bn(self.conv2, self.bn2, h, sv, residual=x)
+        from .fold import conv_bn   # (fold imports this module for SparseBatchNorm)
+        return self._walk(conv_bn, x, sv)
 
 
 __all__ = ["SparseBatchNorm", "SparseResBlock", "sparse_batch_norm"]

@@ -26,6 +26,7 @@ from dataclasses import dataclass
 import torch
 
 from .data import RaggedBatch
+from .fold import FOLDED, MODULES, argmax_labels
 from .pointhead import point_head, point_head_loss, point_lift_mean
 from .pointvoxel import devoxelize, point_voxel_map, voxel_mean
 from .segmax import point_lift_max, voxel_max
@@ -88,38 +89,30 @@ class SparseUNet(torch.nn.Module):
     def depth(self) -> int:
         return len(self.widths) - 1
 
-    def forward(self, x, pyr: SparsePyramid):
+    def _walk(self, how, x, pyr):
+        """The network with its layers and blocks applied as how = fold.MODULES or fold.FOLDED says."""
+        layer, block = how
         if pyr.depth != self.depth:
             raise ValueError(f"SparseUNet: {len(self.widths)} widths need a pyramid of depth {self.depth}, got {pyr.depth}")
         skips = []
         for l in range(self.depth):
-            e = self.enc[l](x, pyr.levels[l])
+            e = block(self.enc[l], x, pyr.levels[l])
             skips.append(e)
-            x = self.down_bn[l](self.down[l](e, pyr.links[l]))
-        x = self.bottom(x, pyr.levels[-1])
+            x = layer(self.down[l], self.down_bn[l], e, pyr.links[l])
+        x = block(self.bottom, x, pyr.levels[-1])
         for l in reversed(range(self.depth)):
-            u = self.up_bn[l](self.up[l](x, pyr.links[l]))
-            m = self.merge_bn[l](self.merge[l](u, skips[l], pyr.levels[l]))
-            x = self.dec[l](m, pyr.levels[l])
+            u = layer(self.up[l], self.up_bn[l], x, pyr.links[l])
+            m = layer(self.merge[l], self.merge_bn[l], u, skips[l], pyr.levels[l])
+            x = block(self.dec[l], m, pyr.levels[l])
         return x
+
+    def forward(self, x, pyr: SparsePyramid):
+        return self._walk(MODULES, x, pyr)
 
     def infer(self, x, pyr: SparsePyramid):
         """forward in eval mode, layer for layer, with every convolution -> BatchNorm pair as one kernel
         (fold.conv_bn): the running statistics whatever self.training says, no gradient, nothing updated."""
-        from .fold import conv_bn
-        if pyr.depth != self.depth:
-            raise ValueError(f"SparseUNet: {len(self.widths)} widths need a pyramid of depth {self.depth}, got {pyr.depth}")
-        skips = []
-        for l in range(self.depth):
-            e = self.enc[l].infer(x, pyr.levels[l])
-            skips.append(e)
-            x = conv_bn(self.down[l], self.down_bn[l], e, pyr.links[l])
-        x = self.bottom.infer(x, pyr.levels[-1])
-        for l in reversed(range(self.depth)):
-            u = conv_bn(self.up[l], self.up_bn[l], x, pyr.links[l])
-            m = conv_bn(self.merge[l], self.merge_bn[l], u, skips[l], pyr.levels[l])
-            x = self.dec[l].infer(m, pyr.levels[l])
-        return x
+        return self._walk(FOLDED, x, pyr)
 
 
 class SparseUNetSegmentation(torch.nn.Module):
@@ -158,11 +151,12 @@ class SparseUNetSegmentation(torch.nn.Module):
         pyr = sparse_pyramid(sv, self.unet.depth)
         return dev, pyr, point_voxel_map(rb, sv, self.lo, self.hi)
 
-    def _fused_features(self, rb, dev, pyr, pvm):
-        """The U-Net's output on the finest level with the lift fused into the voxel mean (lift="max": the voxel max)."""
+    def _fused_features(self, rb, dev, pyr, pvm, unet=None):
+        """The U-Net's output (unet: self.unet.infer in its place) on the finest level with the lift fused into the
+        voxel mean (lift="max": the voxel max)."""
         fn = point_lift_max if self.lift_mode == "max" else point_lift_mean
         x = fn(rb.points.to(dev, torch.float32), self.lift.weight, self.lift.bias, pvm)
-        return self.unet(x, pyr)
+        return (unet or self.unet)(x, pyr)
 
     def forward(self, rb: RaggedBatch, fused: bool = False):
         """fused=True: the same function through pointhead.point_lift_mean and point_head on the same
@@ -189,12 +183,10 @@ class SparseUNetSegmentation(torch.nn.Module):
         its convolution, on the running statistics), point_head and the argmax (pcs_argmax), under
         torch.no_grad().  self.training, the running buffers and num_batches_tracked are left as they
         are, so it may be called on a model in train() mode."""
-        from .fold import argmax_labels
         with torch.no_grad():
             dev, pyr, pvm = self._levels(rb)
-            fn = point_lift_max if self.lift_mode == "max" else point_lift_mean
-            x = fn(rb.points.to(dev, torch.float32), self.lift.weight, self.lift.bias, pvm)
-            logits = point_head(self.unet.infer(x, pyr), pvm, self.head.weight, self.head.bias)
+            x = self._fused_features(rb, dev, pyr, pvm, self.unet.infer)
+            logits = point_head(x, pvm, self.head.weight, self.head.bias)
             labels = argmax_labels(logits)
         return (labels, logits) if return_logits else labels
 

@@ -165,6 +165,25 @@ def _conv_operands(x, wk, bias, taps, align):
     return _pad_channels(x, cin_k), _bf16_2d(wk, cout_k, taps * cin_k), bk, cin_k, cout_k
 
 
+def _unpad(y, cout):
+    """y without the output channels _conv_operands padded."""
+    return y if y.shape[-1] == cout else y[..., :cout].contiguous()
+
+
+def _kernel_weight(weight, transposed=False):
+    """The kernel layout [Cout, taps * Cin] of a parameter in torch's: Conv3d's [Cout, Cin, k, k, k] or
+    (transposed) ConvTranspose3d's [Cin, Cout, k, k, k]."""
+    w = weight.permute(1, 2, 3, 4, 0) if transposed else weight.permute(0, 2, 3, 4, 1)
+    return w.reshape(w.shape[0], -1)
+
+
+def _layer(fn, forward, epi, *args):
+    """One convolution layer, dense or sparse: fn.apply(*args) under autograd, whose forward is
+    forward(*args); with an epilogue (fold.conv_bn, inference) that function alone, with nothing kept
+    for a backward.  Either way the operands, the route and the launch are forward's."""
+    return fn.apply(*args) if epi is None else forward(*args, epi=epi)[0]
+
+
 def _weight_t(wb, taps):
     """wb [Cout, taps * Cin] transposed per tap (pcs_conv3d_weight_t): an input gradient's weight."""
     cout_k, cin_k = wb.shape[0], wb.shape[1] // taps
@@ -186,6 +205,28 @@ def _wgrad(name, head, nbytes, taps, cin, cout, cin_k, cout_k, has_bias, dev):
     return dwk, db
 
 
+def _conv3d_forward(x, wk, bias, k, s, p, transposed, out_dtype, op, epi=None):
+    """The forward of every single-source dense convolution, unfused (pcs_conv3d) or with the epilogue
+    epi of fold.conv_bn (pcs_conv3d_affine): x bf16 [B, D, H, W, Cin], wk the kernel-layout weight
+    [Cout, k^3 * Cin] (fp32 master).  Returns (y, xk, wb): y without the padded channels, and the
+    operands as the kernel read them, which the backward keeps."""
+    if not x.is_cuda:
+        raise RuntimeError("pcs_amd conv3d runs on a HIP device only (no CPU fallback)")
+    if x.dtype != torch.bfloat16 or x.dim() != 5:
+        raise ValueError("x must be a bf16 [B, D, H, W, C] channels-last voxel grid")
+    B, D, H, W, cin = x.shape
+    cout, taps = wk.shape[0], k ** 3
+    if wk.shape[1] != taps * cin:
+        raise ValueError(f"weight has {wk.shape[1] // taps} input channels, x has {cin}")
+    xk, wb, bk, cin_k, cout_k = _conv_operands(x, wk, bias, taps, DENSE_CH_ALIGN)
+    g = _geom(B, (D, H, W), cin_k, cout_k, k, s, p, transposed, op)
+    epi = epi and epi(cout, cout_k, (B, g.Do, g.Ho, g.Wo, cout), x.device)
+    y = torch.empty(B, g.Do, g.Ho, g.Wo, cout_k, dtype=out_dtype, device=x.device)
+    L.forward_call("pcs_conv3d", (g, xk, wb, bk, y, L.dtype_code(out_dtype, what="out_dtype")), epi,
+                   L.stream_ptr(x.device))
+    return _unpad(y, cout), xk, wb
+
+
 class _Conv3dFn(torch.autograd.Function):
     """y = conv(x, w) + b with w in kernel layout [Cout, taps * Cin] (fp32 master).  Multiples of
     32 run natively (a 32-channel U-Net level on 32-channel tiles); other channel counts (a first
@@ -193,21 +234,10 @@ class _Conv3dFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wk, bias, k, s, p, transposed, out_dtype, op):
-        if not x.is_cuda:
-            raise RuntimeError("pcs_amd conv3d runs on a HIP device only (no CPU fallback)")
-        if x.dtype != torch.bfloat16 or x.dim() != 5:
-            raise ValueError("x must be a bf16 [B, D, H, W, C] channels-last voxel grid")
-        B, D, H, W, cin = x.shape
-        cout, taps = wk.shape[0], k ** 3
-        if wk.shape[1] != taps * cin:
-            raise ValueError(f"weight has {wk.shape[1] // taps} input channels, x has {cin}")
-        xk, wb, bk, cin_k, cout_k = _conv_operands(x, wk, bias, taps, DENSE_CH_ALIGN)
-        g = _geom(B, (D, H, W), cin_k, cout_k, k, s, p, transposed, op)
-        y = torch.empty(B, g.Do, g.Ho, g.Wo, cout_k, dtype=out_dtype, device=x.device)
-        L.call("pcs_conv3d", g, xk, wb, bk, y, L.dtype_code(out_dtype, what="out_dtype"), L.stream_ptr(x.device))
+        y, xk, wb = _conv3d_forward(x, wk, bias, k, s, p, transposed, out_dtype, op)
         ctx.save_for_backward(xk, wb)
-        ctx.cfg = (k, s, p, transposed, bias is not None, op, cin, cout)
-        return y if cout_k == cout else y[..., :cout].contiguous()
+        ctx.cfg = (k, s, p, transposed, bias is not None, op, x.shape[-1], wk.shape[0])
+        return y
 
     @staticmethod
     def backward(ctx, dy):
@@ -243,22 +273,25 @@ class _Conv3dFn(torch.autograd.Function):
         return dx, dwk, db, None, None, None, None, None, None
 
 
+def _conv3d(x, weight, bias, stride, padding, out_dtype, epi=None, transposed=False, output_padding=0):
+    """conv3d / conv_transpose3d, or (epi) the same layer under fold.conv_bn's epilogue."""
+    op = output_padding
+    op = (int(op),) * 3 if isinstance(op, int) else tuple(int(o) for o in op)
+    return _layer(_Conv3dFn, _conv3d_forward, epi, x, _kernel_weight(weight, transposed), bias, weight.shape[2],
+                  int(stride), int(padding), transposed, out_dtype, op)
+
+
 def conv3d(x, weight, bias=None, stride=1, padding=0, out_dtype=torch.bfloat16):
     """torch.nn.functional.conv3d on a channels-last bf16 grid x [B, D, H, W, Cin];
     weight [Cout, Cin, k, k, k] (torch layout, fp32), bias [Cout] or None."""
-    cout, cin, k = weight.shape[0], weight.shape[1], weight.shape[2]
-    wk = weight.permute(0, 2, 3, 4, 1).reshape(cout, k ** 3 * cin)
-    return _Conv3dFn.apply(x, wk, bias, k, int(stride), int(padding), False, out_dtype, 0)
+    return _conv3d(x, weight, bias, stride, padding, out_dtype)
 
 
 def conv_transpose3d(x, weight, bias=None, stride=2, padding=0, out_dtype=torch.bfloat16, output_padding=0):
     """torch.nn.functional.conv_transpose3d on a channels-last bf16 grid x [B, D, H, W, Cin];
     weight [Cin, Cout, k, k, k] (torch layout, fp32), bias [Cout] or None; output_padding as
     torch's (an int or 3 ints, each < stride)."""
-    cin, cout, k = weight.shape[0], weight.shape[1], weight.shape[2]
-    wk = weight.permute(1, 2, 3, 4, 0).reshape(cout, k ** 3 * cin)
-    op = (int(output_padding),) * 3 if isinstance(output_padding, int) else tuple(int(o) for o in output_padding)
-    return _Conv3dFn.apply(x, wk, bias, k, int(stride), int(padding), True, out_dtype, op)
+    return _conv3d(x, weight, bias, stride, padding, out_dtype, None, True, output_padding)
 
 
 class Conv3d(torch.nn.Module):
@@ -271,8 +304,11 @@ class Conv3d(torch.nn.Module):
         self.weight, self.bias = ref.weight, ref.bias
         self.stride, self.padding = stride, padding
 
+    def _conv(self, epi, x, out_dtype):   # forward, or with epi the layer under fold.conv_bn
+        return _conv3d(x, self.weight, self.bias, self.stride, self.padding, out_dtype, epi)
+
     def forward(self, x, out_dtype=torch.bfloat16):
-        return conv3d(x, self.weight, self.bias, self.stride, self.padding, out_dtype)
+        return self._conv(None, x, out_dtype)
 
 
 class ConvTranspose3d(torch.nn.Module):
@@ -285,12 +321,31 @@ class ConvTranspose3d(torch.nn.Module):
         self.weight, self.bias = ref.weight, ref.bias
         self.stride, self.padding, self.output_padding = stride, padding, output_padding
 
+    def _conv(self, epi, x, out_dtype):
+        return _conv3d(x, self.weight, self.bias, self.stride, self.padding, out_dtype, epi, True, self.output_padding)
+
     def forward(self, x, out_dtype=torch.bfloat16):
-        return conv_transpose3d(x, self.weight, self.bias, self.stride, self.padding, out_dtype, self.output_padding)
+        return self._conv(None, x, out_dtype)
 
 
 # ---- the two-source stencil (pcs_conv3d_cat*, include/pcs_dense.h): a decoder's convolution of
 # (up, skip) without the concatenated grid
+def _conv3d_cat_forward(xa, xb, wk, bias, out_dtype, epi=None):
+    """_conv3d_forward (k = 3, s = 1, p = 1) on [xa | xb] along channels, ca, cb and cout multiples of 32
+    (pcs_conv3d_cat; pcs_conv3d_cat_affine with the epilogue epi).  Returns (y, xa, xb, wb)."""
+    B, D, H, W, ca = xa.shape
+    cb, cout = xb.shape[-1], wk.shape[0]
+    xa, xb = xa.contiguous(), xb.contiguous()
+    wb = _bf16_2d(wk, cout, 27 * (ca + cb))
+    bk = None if bias is None else bias.float().contiguous()
+    g = _geom(B, (D, H, W), ca + cb, cout, 3, 1, 1, False)
+    epi = epi and epi(cout, cout, (B, D, H, W, cout), xa.device)
+    y = torch.empty(B, D, H, W, cout, dtype=out_dtype, device=xa.device)
+    L.forward_call("pcs_conv3d_cat", (g, xa, ca, xb, cb, wb, bk, y, L.dtype_code(out_dtype, what="out_dtype")), epi,
+                   L.stream_ptr(xa.device))
+    return y, xa, xb, wb
+
+
 class _Conv3dCatFn(torch.autograd.Function):
     """_Conv3dFn (k = 3, s = 1, p = 1) on x = [xa | xb] along channels (ca, cb and cout multiples of
     32), which is never built: the kernels read the two grids, autograd keeps xa and xb themselves,
@@ -299,16 +354,8 @@ class _Conv3dCatFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xa, xb, wk, bias, out_dtype):
-        B, D, H, W, ca = xa.shape
-        cb, cout = xb.shape[-1], wk.shape[0]
-        xa, xb = xa.contiguous(), xb.contiguous()
-        wb = _bf16_2d(wk, cout, 27 * (ca + cb))
-        bk = None if bias is None else bias.float().contiguous()
-        g = _geom(B, (D, H, W), ca + cb, cout, 3, 1, 1, False)
-        y = torch.empty(B, D, H, W, cout, dtype=out_dtype, device=xa.device)
-        L.call("pcs_conv3d_cat", g, xa, ca, xb, cb, wb, bk, y, L.dtype_code(out_dtype, what="out_dtype"),
-               L.stream_ptr(xa.device))
-        ctx.save_for_backward(xa, xb, wb)
+        y, *saved = _conv3d_cat_forward(xa, xb, wk, bias, out_dtype)
+        ctx.save_for_backward(*saved)
         ctx.has_bias = bias is not None
         return y
 
@@ -341,14 +388,8 @@ class _Conv3dCatFn(torch.autograd.Function):
         return dxa, dxb, dwk, db, None
 
 
-def conv3d_cat(xa, xb, weight, bias=None, out_dtype=torch.bfloat16):
-    """conv3d(torch.cat([xa, xb], -1), weight, bias, stride=1, padding=1) without the concatenated
-    grid, and bit-identical to it (the same k-step and summation order): xa bf16 [B, D, H, W, CA], xb
-    bf16 [B, D, H, W, CB], weight [Cout, CA + CB, 3, 3, 3] (the concatenated layer's, fp32), bias
-    [Cout] or None.  The forward writes and autograd keeps no [.., CA + CB] tensor, and the backward
-    writes the two input gradients from one stencil pass over dy (None for an input that needs none).
-    The two-source kernels take CA, CB and Cout in multiples of 32; any other width runs torch.cat
-    and conv3d (zero-padded there): those shapes have no two-source path."""
+def _conv3d_cat(xa, xb, weight, bias, out_dtype, epi=None):
+    """conv3d_cat, or (epi) the same layer, with the same torch.cat fall-back, under fold.conv_bn's epilogue."""
     if not (xa.is_cuda and xb.is_cuda):
         raise RuntimeError("pcs_amd conv3d runs on a HIP device only (no CPU fallback)")
     for name, t in (("xa", xa), ("xb", xb)):
@@ -366,9 +407,19 @@ def conv3d_cat(xa, xb, weight, bias=None, out_dtype=torch.bfloat16):
     if bias is not None and bias.shape != (cout,):
         raise ValueError(f"bias must be [{cout}]")
     if ca % DENSE_CH_ALIGN or cb % DENSE_CH_ALIGN or cout % DENSE_CH_ALIGN or ca == 0 or cb == 0:
-        return conv3d(torch.cat([xa, xb], -1), weight, bias, 1, 1, out_dtype)
-    wk = weight.permute(0, 2, 3, 4, 1).reshape(cout, 27 * (ca + cb))
-    return _Conv3dCatFn.apply(xa, xb, wk, bias, out_dtype)
+        return _conv3d(torch.cat([xa, xb], -1), weight, bias, 1, 1, out_dtype, epi)
+    return _layer(_Conv3dCatFn, _conv3d_cat_forward, epi, xa, xb, _kernel_weight(weight), bias, out_dtype)
+
+
+def conv3d_cat(xa, xb, weight, bias=None, out_dtype=torch.bfloat16):
+    """conv3d(torch.cat([xa, xb], -1), weight, bias, stride=1, padding=1) without the concatenated
+    grid, and bit-identical to it (the same k-step and summation order): xa bf16 [B, D, H, W, CA], xb
+    bf16 [B, D, H, W, CB], weight [Cout, CA + CB, 3, 3, 3] (the concatenated layer's, fp32), bias
+    [Cout] or None.  The forward writes and autograd keeps no [.., CA + CB] tensor, and the backward
+    writes the two input gradients from one stencil pass over dy (None for an input that needs none).
+    The two-source kernels take CA, CB and Cout in multiples of 32; any other width runs torch.cat
+    and conv3d (zero-padded there): those shapes have no two-source path."""
+    return _conv3d_cat(xa, xb, weight, bias, out_dtype)
 
 
 class Conv3dCat(torch.nn.Module):
@@ -383,7 +434,10 @@ class Conv3dCat(torch.nn.Module):
         self.weight, self.bias = ref.weight, ref.bias
         self.ca, self.cb = ca, cb
 
-    def forward(self, xa, xb, out_dtype=torch.bfloat16):
+    def _conv(self, epi, xa, xb, out_dtype):
         if xa.shape[-1] != self.ca or xb.shape[-1] != self.cb:
             raise ValueError(f"Conv3dCat({self.ca}, {self.cb}): got {xa.shape[-1]} and {xb.shape[-1]} channels")
-        return conv3d_cat(xa, xb, self.weight, self.bias, out_dtype)
+        return _conv3d_cat(xa, xb, self.weight, self.bias, out_dtype, epi)
+
+    def forward(self, xa, xb, out_dtype=torch.bfloat16):
+        return self._conv(None, xa, xb, out_dtype)

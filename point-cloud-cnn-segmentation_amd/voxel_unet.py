@@ -29,10 +29,11 @@ import torch
 
 from . import _lib as L
 from .data import RaggedBatch
+from .fold import FOLDED, MODULES, argmax_labels, conv_bn
 from .pointhead import point_head, point_head_loss, point_lift_mean
 from .pointvoxel import CORNERS, PointVoxelMap, devoxelize, voxel_mean
 from .segmax import point_lift_max, voxel_max
-from .sparse_norm import SparseBatchNorm
+from .sparse_norm import SparseBatchNorm, SparseResBlock, conv_then_bn
 from .voxel import Conv3d, Conv3dCat, ConvTranspose3d, _box
 
 
@@ -78,16 +79,15 @@ class VoxelResBlock(torch.nn.Module):
         self.conv1, self.bn1 = Conv3d(channels, channels, bias=False), VoxelBatchNorm(channels, relu=True)
         self.conv2, self.bn2 = Conv3d(channels, channels, bias=False), VoxelBatchNorm(channels, relu=True)
 
+    _walk = SparseResBlock._walk
+
     def forward(self, x):
-        h = self.bn1(self.conv1(x))
-        return self.bn2(self.conv2(h), residual=x)
+        return self._walk(conv_then_bn, x)
 
     def infer(self, x):
         """forward in eval mode with each BatchNorm folded into its convolution's store (fold.conv_bn):
         the running statistics whatever self.training says, no gradient, nothing updated."""
-        from .fold import conv_bn
-        h = conv_bn(self.conv1, self.bn1, x)
-        return conv_bn(self.conv2, self.bn2, h, residual=x)
+        return self._walk(conv_bn, x)
 
 
 class VoxelUNet(torch.nn.Module):
@@ -124,36 +124,29 @@ class VoxelUNet(torch.nn.Module):
             raise ValueError(f"VoxelUNet: a [B, D, H, W, C] grid with D, H, W divisible by 2**{self.depth} is required, "
                              f"got {list(x.shape)}")
 
-    def infer(self, x):
-        """forward in eval mode, layer for layer, with every convolution -> BatchNorm pair as one kernel
-        (fold.conv_bn): the running statistics whatever self.training says, no gradient, nothing updated."""
-        from .fold import conv_bn
+    def _walk(self, how, x):
+        """The network with its layers and blocks applied as how = fold.MODULES or fold.FOLDED says."""
+        layer, block = how
         self._check_grid(x)
         skips = []
         for l in range(self.depth):
-            e = self.enc[l].infer(x)
+            e = block(self.enc[l], x)
             skips.append(e)
-            x = conv_bn(self.down[l], self.down_bn[l], e)
-        x = self.bottom.infer(x)
+            x = layer(self.down[l], self.down_bn[l], e)
+        x = block(self.bottom, x)
         for l in reversed(range(self.depth)):
-            u = conv_bn(self.up[l], self.up_bn[l], x)
-            m = conv_bn(self.merge[l], self.merge_bn[l], u, skips[l])
-            x = self.dec[l].infer(m)
+            u = layer(self.up[l], self.up_bn[l], x)
+            m = layer(self.merge[l], self.merge_bn[l], u, skips[l])
+            x = block(self.dec[l], m)
         return x
 
     def forward(self, x):
-        self._check_grid(x)
-        skips = []
-        for l in range(self.depth):
-            e = self.enc[l](x)
-            skips.append(e)
-            x = self.down_bn[l](self.down[l](e))
-        x = self.bottom(x)
-        for l in reversed(range(self.depth)):
-            u = self.up_bn[l](self.up[l](x))
-            m = self.merge_bn[l](self.merge[l](u, skips[l]))
-            x = self.dec[l](m)
-        return x
+        return self._walk(MODULES, x)
+
+    def infer(self, x):
+        """forward in eval mode, layer for layer, with every convolution -> BatchNorm pair as one kernel
+        (fold.conv_bn): the running statistics whatever self.training says, no gradient, nothing updated."""
+        return self._walk(FOLDED, x)
 
 
 class VoxelUNetSegmentation(torch.nn.Module):
@@ -188,16 +181,17 @@ class VoxelUNetSegmentation(torch.nn.Module):
                              f"{list(rb.points.shape)}")
         return dev, rb.offsets.numel() - 1, dense_point_map(rb, self.grid, self.lo, self.hi, device=dev)
 
-    def _unet_rows(self, x, B):
-        """The U-Net on per-cell rows [B * grid^3, w_0] (a view of the grid either way)."""
+    def _unet_rows(self, x, B, unet=None):
+        """The U-Net (unet: self.unet.infer in its place) on per-cell rows [B * grid^3, w_0] (a view of the grid
+        either way)."""
         G, c = self.grid, x.shape[1]
-        return self.unet(x.view(B, G, G, G, c)).reshape(B * G * G * G, c)
+        return (unet or self.unet)(x.view(B, G, G, G, c)).reshape(B * G * G * G, c)
 
-    def _fused_features(self, rb, dev, B, pvm):
+    def _fused_features(self, rb, dev, B, pvm, unet=None):
         """The U-Net's output rows with the lift fused into the voxel mean (lift="max": the voxel max)."""
         fn = point_lift_max if self.lift_mode == "max" else point_lift_mean
         x = fn(rb.points.to(dev, torch.float32), self.lift.weight, self.lift.bias, pvm)
-        return self._unet_rows(x, B)
+        return self._unet_rows(x, B, unet)
 
     def forward(self, rb: RaggedBatch, fused: bool = False):
         """fused=True: the same function through pointhead.point_lift_mean and point_head on the same
@@ -223,13 +217,9 @@ class VoxelUNetSegmentation(torch.nn.Module):
         its convolution, on the running statistics), point_head and the argmax (pcs_argmax), under
         torch.no_grad().  self.training, the running buffers and num_batches_tracked are left as they
         are, so it may be called on a model in train() mode."""
-        from .fold import argmax_labels
         with torch.no_grad():
             dev, B, pvm = self._map(rb)
-            fn = point_lift_max if self.lift_mode == "max" else point_lift_mean
-            x = fn(rb.points.to(dev, torch.float32), self.lift.weight, self.lift.bias, pvm)
-            G, c = self.grid, x.shape[1]
-            x = self.unet.infer(x.view(B, G, G, G, c)).reshape(B * G * G * G, c)
+            x = self._fused_features(rb, dev, B, pvm, self.unet.infer)
             logits = point_head(x, pvm, self.head.weight, self.head.bias)
             labels = argmax_labels(logits)
         return (labels, logits) if return_logits else labels
